@@ -4,8 +4,15 @@ Workload (default `c4`, BASELINE.json configs[3]): enwik-style synthetic
 text, 128 KiB independent frames at zstd level 3, a 1 GiB unique frame set
 replicated to one 10 GiB corpus (SURVEY.md §8d allows replication).  One
 step = one zd_decode_async over the whole resident share (K1 tables -> K2
-Huffman -> K3 FSE -> K4 execute).  Inputs are resident in HBM before timing;
-output is verified bit-exact against the source bytes after timing.
+Huffman -> K3 FSE -> K4 execute).  Inputs are resident in HBM before timing.
+
+A plain run sets up, warms up, times the steps and prints the result line
+(`--dump-outputs DIR` also writes what the last timed step decoded).  `--full`
+adds everything else after the timed steps: the bit-exact check of the output
+against the source bytes, the per-kernel and roofline passes, the host and
+device plan times, the host-in / host-out leg, the CPU baselines and (N > 1)
+the gather.  The generated corpus is kept between runs (`--corpus-cache`,
+by default corpus/cache/ in the tree, which build() fills for this workload).
 
 Multi-GPU (torchrun, one process per GPU): by default the one 10 GiB corpus
 is split into contiguous frame ranges balanced by compressed bytes
@@ -72,6 +79,78 @@ def make_corpus(workload: str, unique_bytes: int, seed: int, level: int = 9, c2_
     src = gen.text(unique_bytes, seed=seed)
     data = gen.frames(src, 128 << 10, 3)
     return data, src, None, {"frame_bytes": 128 << 10, "level": 3}, time.time() - t0
+
+
+def default_corpus_cache() -> str:
+    return os.path.join(ROOT, "corpus", "cache")
+
+
+def corpus_key(workload: str, unique_mib: int, seed: int, level: int = 9, c2_mib: int = 64) -> str:
+    """File stem of one generated corpus.  The generator's source and the
+    libzstd that compresses are part of it: another of either is another corpus."""
+    import hashlib
+    from corpus import gen, libzstd
+    h = hashlib.sha256(open(gen.__file__, "rb").read() + str(libzstd.version()).encode()).hexdigest()[:12]
+    lv = f"_L{level}" if workload == "c5" else (f"_{c2_mib}" if workload == "c2" else "")
+    return f"{workload}{lv}_{unique_mib}_{seed}_{h}"
+
+
+def _write_atomic(path: str, data: bytes):
+    tmp = f"{path}.{os.getpid()}.tmp"
+    with open(tmp, "wb") as f:
+        f.write(data)
+    os.replace(tmp, path)
+
+
+def cached_corpus(workload: str, unique_mib: int, seed: int, level: int = 9, c2_mib: int = 64,
+                  cache_dir: str | None = None, need_src: bool = False, keep_src: bool = False):
+    """make_corpus() through a directory of earlier results: (frame set, source
+    bytes or None, replicas override, seconds spent generating).  The frames are
+    seeded, so a kept copy is the same bytes.  The source is read back only when
+    kept (keep_src: a directory the caller named); when it is needed and absent
+    the corpus is generated again."""
+    single = workload in ("c2", "c3", "c3s")
+    stem = os.path.join(cache_dir, corpus_key(workload, unique_mib, seed, level, c2_mib)) if cache_dir else None
+    if stem and os.path.exists(stem + ".zst") and (not need_src or os.path.exists(stem + ".src")):
+        frame_set = open(stem + ".zst", "rb").read()
+        src = open(stem + ".src", "rb").read() if need_src else None
+        return frame_set, src, (1 if single else None), 0.0
+    frame_set, src, reps_override, _, tgen = make_corpus(workload, unique_mib << 20, seed, level, c2_mib)
+    if stem:
+        os.makedirs(cache_dir, exist_ok=True)
+        if not os.path.exists(stem + ".zst"):
+            _write_atomic(stem + ".zst", frame_set)
+        if keep_src and src is not None and not os.path.exists(stem + ".src"):
+            _write_atomic(stem + ".src", src)
+    return frame_set, src, reps_override, tgen
+
+
+def prepare_default_corpus():
+    """The default workload's frames into the in-tree cache (build() calls this,
+    so that a benchmark run does not spend its first half minute generating them)."""
+    return cached_corpus("c4", 1024, 0x5EED, cache_dir=default_corpus_cache())[3]
+
+
+def dump_outputs(path: str, d_dst, total: int, status: int):
+    """--dump-outputs: what the last timed step left in the output buffer, as
+    float32 / float64 .npy files (a few MB, the same positions every run):
+      decoded_len.npy         [status, decoded bytes]
+      decoded_chunk_sums.npy  the byte sum of every 1 MiB of the output, in order
+      decoded_sample.npy      the bytes at 4 Mi seeded positions, ascending"""
+    os.makedirs(path, exist_ok=True)
+    out = d_dst[:total]
+    np.save(os.path.join(path, "decoded_len.npy"), np.array([status, total], dtype=np.float64))
+    chunk, slab = 1 << 20, 1 << 30
+    whole = total // chunk * chunk
+    sums = [out[a:min(a + slab, whole)].view(-1, chunk).sum(dim=1, dtype=torch.int64) for a in range(0, whole, slab)]
+    if total > whole:
+        sums.append(out[whole:].sum(dtype=torch.int64).reshape(1))
+    sums = torch.cat(sums).cpu().numpy() if sums else np.zeros(0, dtype=np.int64)
+    np.save(os.path.join(path, "decoded_chunk_sums.npy"), sums.astype(np.float64))
+    n = min(total, 4 << 20)
+    pos = np.sort(np.random.default_rng(0xD0C0DED).integers(0, max(total, 1), size=n))
+    sample = out[torch.from_numpy(pos).to(out.device)].cpu().numpy()
+    np.save(os.path.join(path, "decoded_sample.npy"), sample.astype(np.float32))
 
 
 def host_cores():
@@ -333,17 +412,25 @@ def main():
                          "1024 makes its roofline an HBM figure)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N>1: one corpus split across the ranks (strong) or one corpus per rank (weak)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also: verify the output against the source bytes, the per-kernel "
+                         "and roofline passes, host / device plan times, the host-in / host-out leg, the CPU "
+                         "baselines, and (N>1) the gather")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step decoded (a fixed sample, byte sums of every MiB, status "
+                         "and length) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the check against the source bytes")
     ap.add_argument("--graph", action="store_true", help="time a captured HIP graph of the decode, not its launches")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every core this process may use")
     ap.add_argument("--corpus-cache", default=os.environ.get("ZD_CORPUS_CACHE"),
-                    help="directory to keep the generated corpus in between runs (experiments)")
+                    help="directory to keep the generated corpus in between runs, source bytes included "
+                         "(default: corpus/cache/ in the tree, compressed frames only; '' generates every run)")
     ap.add_argument("--gather", choices=["auto", "on", "off"], default="auto",
                     help="N>1: time gathering every rank's output to rank 0 over RCCL, reported apart "
-                         "(auto: on for strong scaling)")
+                         "(auto: on for strong scaling with --full)")
     ap.add_argument("--no-host-io", action="store_true",
-                    help="skip the host-in / host-out leg (profiling runs of the device path)")
+                    help="--full: skip the host-in / host-out leg (profiling runs of the device path)")
     ap.add_argument("--share", default=None, metavar="R/N",
                     help="one GPU, one process: decode only rank R's frame range of the N-way strong partition "
                          "(the share one rank of an N-GPU run decodes, measured alone; no gather)")
@@ -353,6 +440,7 @@ def main():
     ap.add_argument("--experiment", action="store_true",
                     help="timing-only variants: do not stop on decode errors")
     args = ap.parse_args()
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -374,22 +462,12 @@ def main():
     assert world == 1 or not args.share, "--share is a one-process option"
     strong = pworld > 1 and args.scaling == "strong" and args.workload != "c3s"
     seed = 0x5EED + (0 if (strong or world == 1) else 7919 * rank)
-    cache = None
-    if args.corpus_cache:
-        os.makedirs(args.corpus_cache, exist_ok=True)
-        lv = f"_L{args.level}" if args.workload == "c5" else (f"_{args.c2_mib}" if args.workload == "c2" else "")
-        cache = os.path.join(args.corpus_cache, f"{args.workload}{lv}_{args.unique_mib}_{seed}")
-    if cache and os.path.exists(cache + ".zst"):
-        frame_set = open(cache + ".zst", "rb").read()
-        src = open(cache + ".src", "rb").read() if os.path.exists(cache + ".src") else None
-        reps_override, tgen = (1 if args.workload in ("c2", "c3", "c3s") else None), 0.0
-    else:
-        frame_set, src, reps_override, meta, tgen = make_corpus(args.workload, args.unique_mib << 20, seed, args.level,
-                                                                    args.c2_mib)
-        if cache:
-            open(cache + ".zst", "wb").write(frame_set)
-            if src is not None:
-                open(cache + ".src", "wb").write(src)
+    # the source bytes are what --full checks the output against; a plain run
+    # needs the compressed frames only
+    named = bool(args.corpus_cache)
+    cache_dir = args.corpus_cache if args.corpus_cache is not None else default_corpus_cache()
+    frame_set, src, reps_override, tgen = cached_corpus(args.workload, args.unique_mib, seed, args.level, args.c2_mib,
+                                                        cache_dir or None, need_src=full, keep_src=named)
     reps = reps_override or args.replicas
     set_frames = frames_index(frame_set)[0]
     n_global = len(set_frames) * reps
@@ -408,18 +486,22 @@ def main():
     # allocation and upload) is built once per input, outside the timed
     # region; its wall time is reported beside value as host_plan_ms
     # (a plan over the first frame first: HIP runtime / code-object set-up is
-    # a one-time process cost, not part of planning an input)
-    f0 = set_frames[0]
-    Plan(frame_set[f0["src_offset"]:f0["src_offset"] + f0["src_size"]]).close()
+    # a one-time process cost, not part of planning an input); --full only,
+    # a plain run builds its one plan
+    host_plan_first_s = host_plan_s = None
+    if full:
+        f0 = set_frames[0]
+        Plan(frame_set[f0["src_offset"]:f0["src_offset"] + f0["src_size"]]).close()
+        t0 = time.time()
+        plan = Plan(data)
+        host_plan_first_s = time.time() - t0
+        # steady state: the plan of a next input of this shape (the destroyed
+        # plan's device workspace is reused from libzd's cache, zd_trim_cache)
+        plan.close()
     t0 = time.time()
     plan = Plan(data)
-    host_plan_first_s = time.time() - t0
-    # steady state: the plan of a next input of this shape (the destroyed
-    # plan's device workspace is reused from libzd's cache, zd_trim_cache)
-    plan.close()
-    t0 = time.time()
-    plan = Plan(data)
-    host_plan_s = time.time() - t0
+    if full:
+        host_plan_s = time.time() - t0
     info = plan.info
     log(f"[rank {rank}] plan: {info.nframes} frames, {info.ncompressed} compressed blocks, "
         f"{info.nsequences} sequences, out {info.out_bytes / 2**30:.2f} GiB, ws {info.workspace_bytes / 2**30:.2f} GiB, "
@@ -432,9 +514,9 @@ def main():
     stream = torch.cuda.current_stream(dev)
     sptr = stream.cuda_stream
     # the same plan with the frame/block header walk on the GPU
-    # (zd_plan_create_device: the input is resident in HBM), warm
+    # (zd_plan_create_device: the input is resident in HBM), warm (--full)
     dev_plan_ms = None
-    if not args.experiment:
+    if full and not args.experiment:
         torch.cuda.synchronize(dev)
         for _ in range(2):
             t0 = time.time()
@@ -494,13 +576,20 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     ms_per_step = float(elapsed.item()) / args.steps
 
-    # ---- verify (outside timing): d_dst as the last timed step left it ----
-    # (the timed configuration itself: fused kernel, K2 | K3 fork and all;
-    # the profiled passes below run after this check)
+    # ---- the decode's own status, then --dump-outputs: d_dst as the last
+    # timed step left it ----
     verified = None
-    st, total, _, _, _ = plan.results(d_dst.data_ptr(), sptr)
+    st, total, _, _, first = plan.results(d_dst.data_ptr(), sptr)
+    assert args.experiment or (st == 0 and total == info.out_bytes), (st, total, first)
     redo_frames = int(plan.refresh_info().fused_redo_frames)
-    if not args.no_verify and src is not None:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     d_dst, int(total), int(st))
+
+    # ---- --full: verify (outside timing), still d_dst as the last timed step
+    # left it (the timed configuration itself: fused kernel, K2 | K3 fork and
+    # all; the profiled passes below run after this check) ----
+    if full and not args.no_verify and src is not None:
         ok = st == 0 and total == info.out_bytes
         if strong:
             ref = torch.frombuffer(bytearray(ref_bytes), dtype=torch.uint8).to(dev)
@@ -519,31 +608,33 @@ def main():
             verified = bool(v.item())
         assert args.experiment or verified, "GPU output differs from the source bytes"
 
-    # ---- the dominant launch of the timed pipeline, as it runs: events on the
-    # plan's stream around every launch group that carries work (K0, the
-    # fused kernel, K4, K4F, the K4J kernels; fork and fusion kept), the
-    # longest one is the roofline's kernel ----
-    nprof = max(2, min(args.steps, 3))
-    plan.set_profiling(2)
-    dts = []
-    for _ in range(nprof):
-        step()
-        dts.append(plan.kernel_times())
-    plan.set_profiling(0)
-    dom_all = {k: float(np.mean([d[k] for d in dts])) for k in dts[0]}
-    dom = max(dom_all, key=dom_all.get)
-    dom_ms = dom_all[dom]
+    dom = dom_ms = dom_all = kt = None
+    if full:
+        # ---- the dominant launch of the timed pipeline, as it runs: events on the
+        # plan's stream around every launch group that carries work (K0, the
+        # fused kernel, K4, K4F, the K4J kernels; fork and fusion kept), the
+        # longest one is the roofline's kernel ----
+        nprof = max(2, min(args.steps, 3))
+        plan.set_profiling(2)
+        dts = []
+        for _ in range(nprof):
+            step()
+            dts.append(plan.kernel_times())
+        plan.set_profiling(0)
+        dom_all = {k: float(np.mean([d[k] for d in dts])) for k in dts[0]}
+        dom = max(dom_all, key=dom_all.get)
+        dom_ms = dom_all[dom]
 
-    # ---- per-kernel breakdown (events between launches on the same stream:
-    # the launches one after another, no fork, no fused kernel) ----
-    plan.set_profiling(True)
-    kt = {}
-    for _ in range(nprof):
-        step()
-        for k, v in plan.kernel_times().items():
-            kt.setdefault(k, []).append(v)
-    plan.set_profiling(False)
-    kt = {k: float(np.mean(v)) for k, v in kt.items()}
+        # ---- per-kernel breakdown (events between launches on the same stream:
+        # the launches one after another, no fork, no fused kernel) ----
+        plan.set_profiling(True)
+        kt = {}
+        for _ in range(nprof):
+            step()
+            for k, v in plan.kernel_times().items():
+                kt.setdefault(k, []).append(v)
+        plan.set_profiling(False)
+        kt = {k: float(np.mean(v)) for k, v in kt.items()}
 
     # ---- chunks on parallel streams (an experiment: reported apart) ----
     overlap = None
@@ -601,7 +692,7 @@ def main():
         dist.all_reduce(total_out)
         dist.all_reduce(total_alg)
     gather = None
-    if dist and (args.gather == "on" or (args.gather == "auto" and strong)):
+    if dist and (args.gather == "on" or (args.gather == "auto" and strong and full)):
         comm = shard.Comm(rank, world, dev)
         all_out = int(total_out.item())
         root = torch.empty(all_out + 64 if rank == 0 else 1, dtype=torch.uint8, device=dev)
@@ -640,7 +731,7 @@ def main():
     # host through pinned chunks, plan-owned device buffers (rank 0 only, the
     # other ranks wait: one PCIe link measured alone)
     host_io = None
-    if rank == 0 and not args.experiment and not args.no_host_io:
+    if full and rank == 0 and not args.experiment and not args.no_host_io:
         host_io = host_io_leg(plan, data, info, src if not strong else ref_bytes, reps if not strong else 1)
         del plan_io_scratch[:]
     if dist:
@@ -648,13 +739,15 @@ def main():
 
     value = total_out.item() / (ms_per_step / 1e3) / 1e6
     alg_per_launch = out_bytes + comp_bytes          # C + D, this rank's launch
-    achieved = alg_per_launch / (dom_ms / 1e3) / 1e9
-    # a fraction above 1 would mean the timed launch is not the one doing the
-    # work (the algorithmic bytes cannot move faster than the HBM peak)
-    assert args.experiment or achieved <= HBM_PEAK_GBS, (dom, dom_ms, achieved)
+    pipeline = alg_per_launch / (ms_per_step / 1e3) / 1e9
+    if full:
+        achieved = alg_per_launch / (dom_ms / 1e3) / 1e9
+        # a fraction above 1 would mean the timed launch is not the one doing the
+        # work (the algorithmic bytes cannot move faster than the HBM peak)
+        assert args.experiment or achieved <= HBM_PEAK_GBS, (dom, dom_ms, achieved)
 
     cpu = cpu_zstd = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and src is not None:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and src is not None:
         threads, note = host_cores()
         if args.cpu_threads:
             threads = args.cpu_threads
@@ -709,45 +802,53 @@ def main():
                 "step": "zd_decode_async over every resident frame" +
                         (", replayed from a captured HIP graph" if args.graph else ", launched per step"),
             },
+            # the whole step against the HBM peak; --full adds the dominant
+            # launch (roofline.kernel, achieved, frac) from passes of its own
             "roofline": {
                 "bound": "hbm",
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "alg_bytes_per_launch": int(alg_per_launch),
+                "pipeline_achieved": round(pipeline, 1),
+                "pipeline_frac": round(pipeline / HBM_PEAK_GBS, 4),
+            },
+            "full": full,
+            "fused_redo_frames": redo_frames,
+            "verified_bit_exact": verified,
+        }
+        if full:
+            res["roofline"].update({
                 "kernel": dom,
                 "kernel_ms": round(dom_ms, 3),
                 "launch_groups_ms": {k: round(v, 3) for k, v in dom_all.items()},
                 "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 4),
                 "traffic": traffic_of(dom, args, world),
                 "traffic_unit": "GB per launch (rocprofv3 2 x FETCH_SIZE + WRITE_SIZE, the x2 calibrated on K4's own "
                                 "access patterns: profiles/r3_fetch_calibration.txt; profiles/traffic.json)",
                 "traffic_commit": traffic_commit(),
-                "alg_bytes_per_launch": int(alg_per_launch),
-                "pipeline_achieved": round(alg_per_launch / (ms_per_step / 1e3) / 1e9, 1),
-                "pipeline_frac": round(alg_per_launch / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-            },
-            "kernel_ms": {k: round(v, 3) for k, v in kt.items()},
-            "kernel_ms_note": "kernel_ms: a profiled pass with the launches one after another (no K2 | K3 fork, "
-                              "no fused kernel); roofline.kernel_ms: the dominant launch of the timed pipeline "
-                              "as it runs (HIP events on its stream around it)",
-            "fused_redo_frames": redo_frames,
-            "host_plan_ms": round(host_plan_s * 1e3, 1),
-            "host_plan_first_ms": round(host_plan_first_s * 1e3, 1),
-            "device_walk_plan_ms": None if dev_plan_ms is None else round(dev_plan_ms, 1),
-            "host_plan_split_ms": {"headers_and_descriptors": round(info.host_ns / 1e6, 1),
-                                   "workspace_alloc_and_upload": round(info.device_ns / 1e6, 1)},
-            "value_incl_host_plan": round(total_out.item() / (ms_per_step / 1e3 + host_plan_s) / 1e6, 1),
-            # the same with the plan built on the GPU from the HBM-resident input
-            # (zd_plan_create_device: header walk + descriptors), one plan per step
-            "value_incl_device_plan": None if dev_plan_ms is None else
-            round(total_out.item() / (ms_per_step / 1e3 + dev_plan_ms / 1e3) / 1e6, 1),
-            "h2d_ms": None if not host_io else host_io["h2d_ms"],
-            "d2h_ms": None if not host_io else host_io["d2h_ms"],
-            "host_io": host_io,
-            "cpu_baseline": cpu,
-            "cpu_libzstd": cpu_zstd,
-            "verified_bit_exact": verified,
-        }
+            })
+            res.update({
+                "kernel_ms": {k: round(v, 3) for k, v in kt.items()},
+                "kernel_ms_note": "kernel_ms: a profiled pass with the launches one after another (no K2 | K3 fork, "
+                                  "no fused kernel); roofline.kernel_ms: the dominant launch of the timed pipeline "
+                                  "as it runs (HIP events on its stream around it)",
+                "host_plan_ms": round(host_plan_s * 1e3, 1),
+                "host_plan_first_ms": round(host_plan_first_s * 1e3, 1),
+                "device_walk_plan_ms": None if dev_plan_ms is None else round(dev_plan_ms, 1),
+                "host_plan_split_ms": {"headers_and_descriptors": round(info.host_ns / 1e6, 1),
+                                       "workspace_alloc_and_upload": round(info.device_ns / 1e6, 1)},
+                "value_incl_host_plan": round(total_out.item() / (ms_per_step / 1e3 + host_plan_s) / 1e6, 1),
+                # the same with the plan built on the GPU from the HBM-resident input
+                # (zd_plan_create_device: header walk + descriptors), one plan per step
+                "value_incl_device_plan": None if dev_plan_ms is None else
+                round(total_out.item() / (ms_per_step / 1e3 + dev_plan_ms / 1e3) / 1e6, 1),
+                "h2d_ms": None if not host_io else host_io["h2d_ms"],
+                "d2h_ms": None if not host_io else host_io["d2h_ms"],
+                "host_io": host_io,
+                "cpu_baseline": cpu,
+                "cpu_libzstd": cpu_zstd,
+            })
         if gather:
             res["gather_to_rank0"] = gather
         if overlap:

@@ -7,7 +7,7 @@ export ZD_CORPUS_CACHE=/tmp/zdc
 m=$1; kv=$2
 for e in "" "$kv"; do
   tag=${e:-default}; tag=${tag//[=,]/_}
-  env $e timeout -k 10 600 python bench.py --unique-mib $m --replicas 8 --no-cpu-baseline --no-host-io \
-    > gpurun_out/share_env_${m}_$tag.json 2> gpurun_out/share_env_${m}_$tag.err || exit 1
+  env $e timeout -k 10 600 python bench.py --full --unique-mib $m --replicas 8 --no-cpu-baseline --no-host-io \
+    > ${OUT:-bench_out}/share_env_${m}_$tag.json 2> ${OUT:-bench_out}/share_env_${m}_$tag.err || exit 1
   echo "$m $tag done"
 done

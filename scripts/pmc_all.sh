@@ -5,15 +5,15 @@
 # usage: scripts/pmc_all.sh TAG [UMIB REPS]
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+mkdir -p ${OUT:-bench_out}
 export TMPDIR=/tmp
 export ZD_CORPUS_CACHE=/tmp/zdc
 tag=$1; umib=${2:-1024}; reps=${3:-10}
-B="python bench.py --steps 1 --warmup 1 --unique-mib $umib --replicas $reps --no-cpu-baseline --no-verify"
-timeout -k 10 120 rocprofv3 -L > gpurun_out/counters_list.txt 2>&1 || true
+B="python bench.py --full --steps 1 --warmup 1 --unique-mib $umib --replicas $reps --no-cpu-baseline --no-verify"
+timeout -k 10 120 rocprofv3 -L > ${OUT:-bench_out}/counters_list.txt 2>&1 || true
 pass() {  # name counters...
   local name=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -d gpurun_out/pmc_${tag}_$name -o run --output-format csv -- $B > gpurun_out/pmc_${tag}_$name.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -d ${OUT:-bench_out}/pmc_${tag}_$name -o run --output-format csv -- $B > ${OUT:-bench_out}/pmc_${tag}_$name.log 2>&1
   local rc=$?
   echo "pmc $name rc=$rc"
   return $rc
@@ -24,4 +24,4 @@ pass tcc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum &&
 pass fetch FETCH_SIZE &&
 pass write WRITE_SIZE &&
 pass grbm GRBM_GUI_ACTIVE GRBM_COUNT &&
-python scripts/pmc_summary.py gpurun_out/pmc_${tag}_* > gpurun_out/pmc_${tag}_summary.txt
+python scripts/pmc_summary.py ${OUT:-bench_out}/pmc_${tag}_* > ${OUT:-bench_out}/pmc_${tag}_summary.txt
