@@ -1989,6 +1989,147 @@ __device__ int seq_chainq(const uint8_t* bs, uint32_t bs_size, uintptr_t base, c
   return (mx >= K3F_BAD || ymin < 0 || pl < 0 || E > pl) ? 1 : 0;
 }
 
+// seq_chainq with every window used by two steps: a ring of R windows, steps
+// 2j and 2j + 1 select from slot j mod R.  The slot is free after step 2j + 1
+// and is loaded again D steps later, at the position after step 2j + 1 + D,
+// for steps 2j + 2R and 2j + 2R + 1: 2R - 2 - D whole steps lie between a load
+// and its first use, and the window has to cover the 2R - D steps after its
+// load, 32 N - 7 bits together.  R = 3, N = 6:
+//   D = 0: 4 steps between, 6 steps covered (~30 bits a step);
+//   D = 1: 3 steps between (seq_chainq's), 5 covered (~37 bits a step);
+//   D = 2: 2 steps between, 4 covered (~46 bits a step, seq_chainq's).
+// Either way the chain issues half of seq_chainq's window loads.  A window
+// that did not cover its step drives ymin negative as in seq_chainq, so
+// zd_k_sequences_q runs this chain only in waves whose blocks all average few
+// bits a sequence (K3H_BITS).  Vector-memory order: a pair's store follows its
+// first step and the reloads sit between stores, so the wait for a slot's
+// load leaves the younger stores and loads in flight.  A trip is 2R steps: its
+// first two pairs are <= the spare pair as in seq_chainq, the later ones are
+// clamped to it.  Records, epilogue and rejects are seq_chainq's.
+#ifndef ZD_K3H_RING
+#define ZD_K3H_RING 3                // windows in the ring
+#endif
+#ifndef ZD_K3H_DELAY
+#define ZD_K3H_DELAY 1               // steps between a slot's last use and its reload
+#endif
+#ifndef ZD_K3H_BITS
+#define ZD_K3H_BITS 26               // a wave takes seq_chainqh when 8 * bs_size <= this * nseq in all its blocks
+#endif
+// the slot step t of a trip reloads after its select (-1: none)
+template <int R, int D>
+__device__ constexpr int k3h_reload(int t) {
+  const int x = t - 1 - D + (t - 1 - D < 0 ? 2 * R : 0);
+  return x % 2 == 0 ? (x / 2) % R : -1;
+}
+template <int R, int D, int N>
+__device__ int seq_chainqh(const uint8_t* bs, uint32_t bs_size, uintptr_t base, const lds_u16* tab, int role,
+                           int all, int alo, int alm, uint32_t n, uint64_t* __restrict__ out) {
+  static_assert(R >= 2 && D >= 0 && D <= 2 * R - 4, "seq_chainqh: a slot is loaded at least a whole step before its use");
+  constexpr int U = 2 * R;
+  if (bs_size == 0) return 1;
+  const uint8_t lastb = bs[bs_size - 1];
+  if (lastb == 0) return 1;
+  int32_t pos = (int32_t)(8 * (bs_size - 1)) + highbit32(lastb);
+  const int32_t A = all + alo + alm;
+  if (A > pos) return 1;
+  if ((intptr_t)bs - (intptr_t)base + (intptr_t)bs_size < 4 * N) return 1;
+  const int32_t m = (int32_t)max((intptr_t)base - (intptr_t)bs, (intptr_t)(-4 * N));
+  const Win6 wi = win6_load(bs, m, pos);
+  const uint32_t v0 = win6_bits(wi, pos, (uint32_t)A);
+  const int alr = role == 0 ? alo : role == 1 ? alm : all;
+  const uint32_t m3 = role == 3 ? 0u : ~0u, m0 = role == 0 ? 0u : ~0u;
+  const uint32_t ar = (uint32_t)(alr - 31), Tr = 1u << alr;
+  uint32_t s = role == 0 ? __builtin_amdgcn_ubfe(v0, alm, alo)
+             : role == 1 ? __builtin_amdgcn_ubfe(v0, 0, alm)
+             : v0 >> (alo + alm);
+  pos -= A;
+  uint32_t pS = s, pPos = (uint32_t)pos;
+  auto pair_word = [&](uint32_t sB, uint32_t posB) -> uint32_t {
+    const uint32_t d = pS | (sB << 10);
+    const uint32_t x = d | ((pPos - posB) << 20);
+    return role == 3 ? pPos : (role == 0 ? x : d);
+  };
+  g_u32* const outw = (g_u32*)out + role;
+  const uint32_t n_even = (n + 1) & ~1u;              // the spare pair
+  // every slot starts as the window at the first step's position (slot j is
+  // for steps 2j and 2j + 1, or is loaded again before them)
+  WinN<N> w[R];
+  w[0] = winn_load<N>(bs, m, pos);
+  asm volatile("" ::: "memory");
+  outw[0] = pair_word(s, (uint32_t)pos);
+#pragma unroll
+  for (int k = 1; k < R; k++) w[k] = w[0];
+  uint32_t mx = 0;
+  int32_t ymin = 0;
+  auto step = [&](WinN<N>& use, WinN<N>* rl) {
+    const uint32_t e = tab[s];
+    mx = max(mx, e);
+    const uint32_t ns = e & 1023, nb = __builtin_clz(ns) + ar;
+    const uint32_t c = e >> 10;
+    const uint32_t csum = qdpp<0x00>(c) + qdpp<0x55>(c) + qdpp<0xAA>(c);
+    const int32_t y = (pos - use.wb) - (int32_t)csum;
+    pos -= (int32_t)csum;
+    ymin = min(ymin, y);
+    uint32_t r = winn_at_tree<N>(use, (uint32_t)y);
+    if (rl) {
+      // D = 0 only (measurement builds; with D >= 1 the slot reloaded is never
+      // the one in use): the reload goes out after this select, so it lands in
+      // the slot's own registers (issued earlier it takes new ones, and the
+      // copy back at the end of the trip waits for every load of the trip)
+      if (rl == &use) asm volatile("" : "+v"(r) : : "memory");
+      *rl = winn_load<N>(bs, m, pos);
+    }
+    const uint32_t t = qdpp<0x50>(nb) & m0;
+    const uint32_t v = __builtin_amdgcn_ubfe(r, t + qdpp<0x50>(t), nb);
+    s = (ns << nb) + v - Tr;
+  };
+  uint32_t i = 0;
+  // a trip runs while i + 1 < n, so its pairs i, i + 2 are <= n and a pair at
+  // n (n even) is the spare pair; the pairs from i + 4 on can lie past it
+  g_u32* wp = outw;
+  for (; i + 1 < n; i += U) {
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+      const int ra = k3h_reload<R, D>(2 * k), rb = k3h_reload<R, D>(2 * k + 1);
+      step(w[k], ra >= 0 ? &w[ra] : nullptr);
+      asm volatile("" ::: "memory");
+      if (k < 2)
+        wp[4 * k] = pair_word(s, (uint32_t)pos);
+      else
+        outw[2 * min(i + 2 * k, n_even)] = pair_word(s, (uint32_t)pos);
+      step(w[k], rb >= 0 ? &w[rb] : nullptr);
+      pS = s;
+      pPos = (uint32_t)pos;
+    }
+    wp += 4 * R;
+  }
+  // the record the last trip kept (record i): the block's last when n - 1 == i
+  outw[2 * (i < n ? i : n_even)] = pair_word(pS, pPos);
+  const uint64_t rl = k3_reread(out, n - 1);
+  const int32_t pl = (int32_t)(uint32_t)rl;
+  const uint32_t st = (uint32_t)(rl >> 32);
+  const uint32_t shr = role == 0 ? 20 : role == 1 ? 10 : 0;
+  const uint32_t el = tab[(st >> shr) & 1023] & m3;
+  mx = quad_max(max(mx, el));
+  const uint32_t S = quad_sum((__builtin_clz(el & 1023) + ar) & m3);
+  const int32_t E = (int32_t)(quad_sum(el >> 10) - S);
+  return (mx >= K3F_BAD || ymin < 0 || pl < 0 || E > pl) ? 1 : 0;
+}
+
+#ifdef ZD_K3_COUNT
+// experiment builds only: blocks run by K3Q, by the half-window chain among
+// them, and rejects (blocks gone to the exact chain) of each chain
+__device__ unsigned long long zd_k3_count[4];
+extern "C" int zd_debug_k3_count(unsigned long long* v, int reset) {
+  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(zd_k3_count), sizeof(zd_k3_count)) != hipSuccess) return -1;
+  if (reset) {
+    const unsigned long long z[4] = {0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(zd_k3_count), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#endif
+
 #ifndef ZD_K3Q_CHAINS
 #define ZD_K3Q_CHAINS 16
 #endif
@@ -2058,8 +2199,22 @@ __global__ __launch_bounds__(64) void zd_k_sequences_q(const uint8_t* __restrict
   bool exact = !use_lds;
   if (use_lds) {
     const lds_u16* tab = role == 0 ? mine + K3_TL + K3_TM : role == 1 ? mine + K3_TL : mine;
-    exact = seq_chainq<ZD_K3_LA, ZD_K3_WN>(blk + cs.bs_off, cs.bs_size, lo, tab, role, al[0], al[1], al[2], C.nseq,
-                                          recs + C.seq_out) != 0;
+    // the half-window chain when every block of the wave averages few bits a
+    // sequence (its windows cover ~37 bits a step), else seq_chainq for all
+    const bool half = ZD_K3H_BITS > 0 && __ballot(8ull * cs.bs_size > (uint64_t)ZD_K3H_BITS * C.nseq) == 0;
+    if (half)
+      exact = seq_chainqh<ZD_K3H_RING, ZD_K3H_DELAY, ZD_K3_WN>(blk + cs.bs_off, cs.bs_size, lo, tab, role, al[0], al[1], al[2],
+                                                 C.nseq, recs + C.seq_out) != 0;
+    else
+      exact = seq_chainq<ZD_K3_LA, ZD_K3_WN>(blk + cs.bs_off, cs.bs_size, lo, tab, role, al[0], al[1], al[2], C.nseq,
+                                            recs + C.seq_out) != 0;
+#ifdef ZD_K3_COUNT
+    if (role == 0) {
+      atomicAdd(&zd_k3_count[0], 1ull);
+      if (half) atomicAdd(&zd_k3_count[1], 1ull);
+      if (exact) atomicAdd(&zd_k3_count[half ? 3 : 2], 1ull);
+    }
+#endif
   }
   if (exact && role == 0)
     st = K3_CHAIN<g_u16*, true>(blk + cs.bs_off, cs.bs_size, lo, (g_u16*)g[0], (g_u16*)g[2], (g_u16*)g[1], al[0],
