@@ -163,6 +163,13 @@ typedef struct zd_plan zd_plan;
  * one block per wave (zd_k_sequences_l, latency-first) by default; this flag
  * keeps K3Q.  Same records either way; tests run both. */
 #define ZD_F_SEQ_NO_LATENCY 256u
+/* Table-build choice: plans past 64 tables per CU run K1 as two passes -- a
+ * parse pass, one block per lane, and a build pass, one wave per block
+ * (zd_k_tables_parse / zd_k_tables_build) -- unless
+ * ZD_F_K1_LANES is given; this flag runs the two passes in a plan of any size
+ * (before the wave-per-block route; never the sequence half of a fused
+ * plan).  Same tables either way; tests run both. */
+#define ZD_F_K1_SPLIT    512u
 /* Test switch: K4J runs ONE pointer-jumping round of one hop, so a frame
  * whose match chains are deeper keys LS_JROUNDS and zd_plan_decompress plans
  * it again on the streaming executor (tests/test_large_frames.py). */
@@ -217,6 +224,7 @@ typedef struct zd_plan_info {
 #define ZD_ROUTE_K1_SEQ_WAVES 4u   /* K1's sequence half one wave per block */
 #define ZD_ROUTE_FORK         8u   /* K2 beside K3 on a second stream */
 #define ZD_ROUTE_K1_FORK     16u   /* K1's two halves on the two streams */
+#define ZD_ROUTE_K1_SPLIT    32u   /* K1 as a parse pass and a build pass */
 int zd_route(uint32_t cus, uint64_t nframes, uint64_t n_tables, uint64_t n_seq_blocks, uint64_t n_huf_blocks,
              int single_block_frames, uint32_t flags, uint32_t* route);
 
@@ -283,6 +291,13 @@ int zd_plan_checksums(zd_plan* plan, const uint8_t* d_dst, void* stream, int32_t
  * kernels together ("zd_k_jsum+...+zd_k_jround"); the largest is the
  * dominant launch.  0: off.  names/ms arrays of cap entries. */
 int zd_plan_set_profiling(zd_plan* plan, int enable);
+/* The blocks of the last zd_decode_async whose Huffman tree / sequence tables
+ * K1's fast passes left to the large-scratch lane kernels (a table of more
+ * than 64 symbols, a weight table past AL 6, more than 255 weights, maxBits >
+ * 11, a tree that is not complete): waits for `stream`, reads the blocks'
+ * state back and counts the flags.  Nothing on the decode path counts them.
+ * libzstd's frames give (0, 0).  Either pointer may be NULL. */
+int zd_plan_k1_fallbacks(zd_plan* plan, void* stream, uint64_t* huf_blocks, uint64_t* seq_blocks);
 int zd_plan_kernel_times(zd_plan* plan, const char** names, float* ms, int cap, int* n);
 
 /* zd_decompress with a plan already made for the same n bytes (so a caller

@@ -185,6 +185,7 @@ struct RouteIn {
 };
 struct Route {
   bool fused = false, k4f = false, k1_seq_waves = false, fork = false, k1_fork = false, k3_lat = false;
+  bool k1_split = false;
 };
 constexpr uint32_t K4F_MIN_PER_CU = 1, K4F_MAX_PER_CU = 3;
 constexpr uint32_t FUSE_MIN_PER_CU = 1, FUSE_MAX_PER_CU = 4;
@@ -201,6 +202,7 @@ Route route_plan(const RouteIn& in) {
             in.single_block_frames && in.nframes >= FUSE_MIN_PER_CU * cus && in.nframes <= FUSE_MAX_PER_CU * cus;
   r.k4f = !r.fused && in.nframes >= K4F_MIN_PER_CU * cus && in.nframes <= K4F_MAX_PER_CU * cus;
   r.k1_seq_waves = in.n_tables <= K1W_MAX_PER_CU * cus && !(in.flags & ZD_F_K1_LANES);
+  r.k1_split = (in.flags & ZD_F_K1_SPLIT) || (in.n_tables > K1W_MAX_PER_CU * cus && !(in.flags & ZD_F_K1_LANES));
   const uint64_t slots = K3_CHAINS_PER_CU * cus, rem = in.n_seq % slots;
   r.fork = in.n_seq >= cus && rem != 0 && (double)rem <= FORK_MAX_FILL * (double)slots;
   r.k1_fork = !r.fork && in.n_huf && in.n_seq;
@@ -1344,7 +1346,8 @@ int zd_route(uint32_t cus, uint64_t nframes, uint64_t n_tables, uint64_t n_seq_b
   in.flags = flags;
   const Route r = route_plan(in);
   *route = (r.fused ? ZD_ROUTE_FUSED : 0u) | (r.k4f ? ZD_ROUTE_K4F : 0u) | (r.k1_seq_waves ? ZD_ROUTE_K1_SEQ_WAVES : 0u) |
-           (r.fork ? ZD_ROUTE_FORK : 0u) | (r.k1_fork ? ZD_ROUTE_K1_FORK : 0u);
+           (r.fork ? ZD_ROUTE_FORK : 0u) | (r.k1_fork ? ZD_ROUTE_K1_FORK : 0u) |
+           (r.k1_split ? ZD_ROUTE_K1_SPLIT : 0u);
   return ZD_OK;
 }
 
@@ -1545,6 +1548,19 @@ void zd_plan_destroy(zd_plan* P) {
   delete P;
 }
 
+int zd_plan_k1_fallbacks(zd_plan* P, void* stream, uint64_t* huf_blocks, uint64_t* seq_blocks) {
+  if (!P || !P->launched) return ZD_E_INVALID_ARG;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  std::vector<CompState> cs(P->n_comps);
+  if (P->n_comps)
+    HIPCHK(hipMemcpy(cs.data(), P->d_ws + P->W.comp_state, P->n_comps * sizeof(CompState), hipMemcpyDeviceToHost));
+  uint64_t h = 0, q = 0;
+  for (const CompState& c : cs) { h += c.k1_bigh != 0; q += c.k1_bigs != 0; }
+  if (huf_blocks) *huf_blocks = h;
+  if (seq_blocks) *seq_blocks = q;
+  return ZD_OK;
+}
+
 int zd_plan_set_profiling(zd_plan* P, int enable) {
   if (!P || enable < 0 || enable > 2) return ZD_E_INVALID_ARG;
   if (enable && !P->ev_made) {
@@ -1666,6 +1682,7 @@ int zd_decode_async(zd_plan* P, const uint8_t* d_src, uint8_t* d_dst, size_t dst
     a.k1_fork = true;
   }
   a.k1_seq_waves = E.k1w_max >= 0 ? P->n_tables <= (uint64_t)E.k1w_max && !(P->flags & ZD_F_K1_LANES) : r.k1_seq_waves;
+  a.k1_split = r.k1_split;
   a.k3_lat = E.k3l >= 0 ? E.k3l == 1 && !(P->flags & (ZD_F_SEQ_ONE_LANE | ZD_F_SEQ_NO_LATENCY)) : r.k3_lat;
   P->last_fused = P->fused && !P->profile;
   if (P->last_fused) {

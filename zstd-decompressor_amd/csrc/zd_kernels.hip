@@ -5,7 +5,10 @@
 //                      -> LUT, FSE table descriptions -> decode tables
 //                      (huffman.rs:80-203, fse.rs:16-202, sequences.rs:91-187);
 //                      zd_k_tables_seqw: the sequence tables one wave per block;
-//                      zd_k_huf_pairs: each LUT of <= 11 bits -> K2's pair table
+//                      zd_k_huf_pairs: each LUT of <= 11 bits -> K2's pair table;
+//                      plans past one round of builds: zd_k_tables_parse (the
+//                      serial walks, one block per lane) then zd_k_tables_build
+//                      (the tables, one wave per block)
 //   K2 zd_k_huffman    one stream per lane, 8 blocks per wave, pair tables in
 //                      LDS (literals.rs:49-86 + huffman.rs:205-218)
 //   K3 zd_k_sequences_q  the FSE state chain, four lanes per block, 16 blocks
@@ -207,8 +210,8 @@ struct FwBitsW {
 };
 
 // parse_fse_table (fse.rs:16-69); dist holds max_sym entries (256: all)
-template <typename BR>
-__device__ int parse_ncount(BR& in, uint8_t* al_out, int16_t* dist, uint32_t* nsym_out, uint32_t max_sym) {
+template <typename BR, typename D>
+__device__ int parse_ncount(BR& in, uint8_t* al_out, D* dist, uint32_t* nsym_out, uint32_t max_sym) {
   uint32_t v;
   if (int r = in.take(4, &v)) return r;
   int al = (int)v + 5;
@@ -230,7 +233,7 @@ __device__ int parse_ncount(BR& in, uint8_t* al_out, int16_t* dist, uint32_t* ns
     in.skip(short_code ? bits - 1 : bits);
     int32_t proba = decoded - 1;
     remaining -= proba < 0 ? -proba : proba;
-    if (n_sym < max_sym) dist[n_sym] = (int16_t)proba;
+    if (n_sym < max_sym) dist[n_sym] = (D)proba;
     else if (max_sym < 256) return K1_BIG;
     n_sym++;
     if (proba == 0) {
@@ -274,8 +277,10 @@ __device__ uint64_t k1_prof[8];
 #define K1T(v) do { } while (0)
 #define K1ADD(i, a, b) do { } while (0)
 #endif
-__device__ int build_fse(int al, const int16_t* dist, uint32_t nsym, uint16_t* __restrict__ table, uint8_t* sym,
-                         uint16_t* next) {
+// (D / N: the counts' and counters' types; K1's parse pass keeps a weight
+// table's in bytes, next in place of dist)
+template <typename D, typename N>
+__device__ int build_fse(int al, const D* dist, uint32_t nsym, uint16_t* __restrict__ table, uint8_t* sym, N* next) {
   if (al > FSE_MAX_AL) return ZD_E_LARGE_ACCURACY_LOG;
   K1T(t0);
   uint32_t T = 1u << al;
@@ -302,7 +307,7 @@ __device__ int build_fse(int al, const int16_t* dist, uint32_t nsym, uint16_t* _
   if (placed != zero_pos) return ZD_E_CORRUPTED_TABLE;
   K1T(t1);
   K1ADD(0, t0, t1);
-  for (uint32_t s = 0; s < nsym; s++) next[s] = dist[s] > 0 ? (uint16_t)dist[s] : (dist[s] == -1 ? 1 : 0);
+  for (uint32_t s = 0; s < nsym; s++) next[s] = dist[s] > 0 ? (N)dist[s] : (N)(dist[s] == -1 ? 1 : 0);
   // next[s]++ in state order, four states a step (T >= 32): one LDS round
   // trip for the four counters instead of one per state; a symbol met again
   // inside the step continues from its earlier value there, and the
@@ -315,10 +320,10 @@ __device__ int build_fse(int al, const int16_t* dist, uint32_t nsym, uint16_t* _
     const uint32_t t1 = s1 == s0 ? t0 + 1 : n1;
     const uint32_t t2 = s2 == s1 ? t1 + 1 : (s2 == s0 ? t0 + 1 : n2);
     const uint32_t t3 = s3 == s2 ? t2 + 1 : (s3 == s1 ? t1 + 1 : (s3 == s0 ? t0 + 1 : n3));
-    next[s0] = (uint16_t)(t0 + 1);
-    next[s1] = (uint16_t)(t1 + 1);
-    next[s2] = (uint16_t)(t2 + 1);
-    next[s3] = (uint16_t)(t3 + 1);
+    next[s0] = (N)(t0 + 1);
+    next[s1] = (N)(t1 + 1);
+    next[s2] = (N)(t2 + 1);
+    next[s3] = (N)(t3 + 1);
     table[i] = fse_entry(s0, t0);
     table[i + 1] = fse_entry(s1, t1);
     table[i + 2] = fse_entry(s2, t2);
@@ -1060,33 +1065,9 @@ __device__ inline uint32_t pr_one(TP dl, uint32_t L, int p, uint32_t idx, int32_
   return (e >> 16) & 0xFF;
 }
 
-// zd_k_huf_pairs: one wave per block of K1's list that built a LUT of maxBits
-// <= 11: the LUT is staged in LDS, L found by a wave reduction, then the
-// slot is overwritten with the pair table and L.
-constexpr int PR_WAVES = 4;
-__global__ __launch_bounds__(64 * PR_WAVES) void zd_k_huf_pairs(const CompBlock* __restrict__ comp,
-                                                                 const CompState* __restrict__ cstate,
-                                                                 const uint32_t* __restrict__ list, uint32_t n_list,
-                                                                 uint16_t* luts) {
-  __shared__ __attribute__((aligned(16))) uint16_t u[PR_WAVES][1 << K2_LUT_BITS];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint32_t li = blockIdx.x * PR_WAVES + wv;
-  if (li >= n_list) return;                        // whole waves: no workgroup barrier below
-  const uint32_t ci = list[li];
-  const CompBlock& C = comp[ci];
-  if (C.lit_type != LIT_COMPRESSED || C.host_stage <= PS_HUF_DESC || C.prebuilt) return;
-  const int p = cstate[ci].huf_bits;
-  if (p == 0 || p > K2_LUT_BITS) return;
-  uint16_t* slot = luts + (uint64_t)C.lut_slot * LUT_ENTRIES;
-  const lds_u16* U = (const lds_u16*)u[wv];
-  {                                                // 16 bytes per lane and step
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const int n16 = (1 << p) / 8;
-    if (n16 == 0) { if (lane < (1 << p)) u[wv][lane] = slot[lane]; }
-    else for (int e = lane; e < n16; e += 64) ((u32x4*)u[wv])[e] = ((const u32x4*)slot)[e];
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+// A wave's conversion of the u16 LUT U (LDS, maxBits p <= 11) into the pair
+// table and L of `slot`: L found by a wave reduction.
+__device__ inline void pr_convert(const lds_u16* U, int p, uint16_t* slot, int lane) {
   // deep(i): the 10-bit prefix i starts with an 11-bit code or absent node
   auto deep = [&](uint32_t i) {
     return p > PR_BITS && (lut_width(U[2 * i], true) > PR_BITS || lut_width(U[2 * i + 1], true) > PR_BITS);
@@ -1114,6 +1095,38 @@ __global__ __launch_bounds__(64 * PR_WAVES) void zd_k_huf_pairs(const CompBlock*
     dl[j] = ent;
   }
   if (lane == 0) dl[PR_L_AT] = L;
+}
+
+// zd_k_huf_pairs: one wave per block of K1's list that built a LUT of maxBits
+// <= 11: the LUT is staged in LDS, then the slot is overwritten with the pair
+// table and L (pr_convert).  only_big: the blocks zd_k_tables<true> built
+// after K1's parse pass alone (1: those flagged k1_bigh, 2: k1_bigs too, the
+// PART 3 launch; the others' pair tables are zd_k_tables_build's).
+constexpr int PR_WAVES = 4;
+__global__ __launch_bounds__(64 * PR_WAVES) void zd_k_huf_pairs(const CompBlock* __restrict__ comp,
+                                                                 const CompState* __restrict__ cstate,
+                                                                 const uint32_t* __restrict__ list, uint32_t n_list,
+                                                                 uint16_t* luts, uint32_t only_big) {
+  __shared__ __attribute__((aligned(16))) uint16_t u[PR_WAVES][1 << K2_LUT_BITS];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t li = blockIdx.x * PR_WAVES + wv;
+  if (li >= n_list) return;                        // whole waves: no workgroup barrier below
+  const uint32_t ci = list[li];
+  const CompBlock& C = comp[ci];
+  if (C.lit_type != LIT_COMPRESSED || C.host_stage <= PS_HUF_DESC || C.prebuilt) return;
+  if (only_big && !(cstate[ci].k1_bigh || (only_big == 2 && cstate[ci].k1_bigs))) return;
+  const int p = cstate[ci].huf_bits;
+  if (p == 0 || p > K2_LUT_BITS) return;
+  uint16_t* slot = luts + (uint64_t)C.lut_slot * LUT_ENTRIES;
+  {                                                // 16 bytes per lane and step
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const int n16 = (1 << p) / 8;
+    if (n16 == 0) { if (lane < (1 << p)) u[wv][lane] = slot[lane]; }
+    else for (int e = lane; e < n16; e += 64) ((u32x4*)u[wv])[e] = ((const u32x4*)slot)[e];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  pr_convert((const lds_u16*)u[wv], p, slot, lane);
 }
 
 // One Huffman stream of a tree of maxBits p <= 11 from its pair table (LDS,
@@ -3504,7 +3517,8 @@ __device__ inline uint32_t lanes_below(uint64_t m) {
 #ifndef ZD_FZ_LANEMASK
 #define ZD_FZ_LANEMASK 1
 #endif
-__device__ int fz_build_fse(int al, const int16_t* dist, uint32_t nsym, uint16_t* tab, FzK1& W, int lane) {
+template <typename WS>
+__device__ int fz_build_fse(int al, const int16_t* dist, uint32_t nsym, uint16_t* tab, WS& W, int lane) {
   if (al > FSE_MAX_AL) return ZD_E_LARGE_ACCURACY_LOG;
   const uint32_t T = 1u << al, mask = T - 1, step = (T >> 1) + (T >> 3) + 3;
   uint32_t nneg = 0, placed = 0;
@@ -3712,6 +3726,304 @@ __global__ __launch_bounds__(64) void zd_k_tables_seqw(const uint8_t* __restrict
   const CompBlock C = comp[ci];
   if (C.prebuilt || C.nseq == 0 || C.host_stage <= PS_SEQ_TABLES) return;
   fz_tables(src, C, ci, cstate, fstate, fses, W, nullptr, I, (int)threadIdx.x, C.frame);
+}
+
+// ---------------------------------------------------------------------------
+// K1 in two passes, for plans past one round of table builds (ZD_ROUTE_K1_SPLIT).
+// zd_k_tables_parse: one block per lane, the serial work alone -- the FSE-coded
+// weight stream (or the direct weights) with from_weights' checks, and the
+// NCount walk of the FSE-mode sequence tables -- leaving a parsed record in the
+// block's own, still unwritten table slots:
+//   LUT slot  bytes 0-255 the weights, the implied last one included;
+//             dword K1R_HDR their number n | maxBits p << 16
+//   FSE slot  table k (FSE mode): its first K1S_SYMS u16 the normalized counts,
+//             dword K1R_FSE_HDR of the table nsym | AL << 16 (0: nothing to build)
+// and the CompState bytes and parse-error keys zd_k_tables leaves.  A table
+// from_distribution builds never fails after its NCount parsed (the counts
+// sum to the table size), so every error is the parse pass's.
+// zd_k_tables_build: one wave per block, the per-entry work -- fz_build_fse
+// into the slot in state order, the Huffman LUT laid out in LDS and converted
+// there to K2's pair table (pr_convert), the only form that goes to HBM.
+// What the two passes do not take (a table of more than K1S_SYMS symbols, a
+// weight table past AL 6, more than 255 weights, maxBits > 11, a tree that is
+// not complete: from_number_of_bits' holes and unplaced codes) the parse pass
+// flags k1_bigh / k1_bigs, and zd_k_tables<true> builds it after them.
+// ---------------------------------------------------------------------------
+constexpr uint32_t K1R_HDR = 64;                   // dword of the LUT slot
+constexpr uint32_t K1R_FSE_HDR = K1S_SYMS / 2;     // dword of a table in the FSE slot
+struct K1LaneP {
+  static constexpr uint32_t SYMS = K1S_SYMS, WFSE = 64;
+  uint16_t fse[64];                                // Huffman-weight FSE table (AL <= 6)
+  uint8_t sym[64];
+  union {
+    int8_t dist[K1S_SYMS];                         // counts of an AL <= 6 table fit a byte
+    uint8_t next[K1S_SYMS];                        // (build_fse: in place of dist)
+  };
+  uint32_t pad;                                    // 65 dwords a lane: the lanes' entries on different banks
+};
+static_assert(sizeof(K1LaneP) == 260, "K1LaneP: 65 dwords");
+
+// HuffmanDecoder::parse + from_weights (huffman.rs:80-131, 177-203) up to the
+// weights: k1_huffman_lane's statuses, K1_BIG for what the build pass does
+// not take.
+__device__ int k1_huffman_parse(const uint8_t* desc, const uint8_t* src, const uint8_t* src_end, K1LaneP& L,
+                                uint32_t* rec, int* p_out) {
+  int st = 0;
+  uint32_t nw = 0, sum = 0, maxw = 0, acc = 0;
+  bool panic = false;
+  const uint8_t h = desc[0];
+  auto put = [&](uint32_t i, uint32_t w) {
+    if (i >= K1_MAX_WEIGHTS) return false;
+    if (w) {
+      if (w - 1 >= 32 || sum > 0xFFFFFFFFu - (1u << (w - 1))) panic = true;
+      else sum += 1u << (w - 1);
+      maxw = w > maxw ? w : maxw;
+    }
+    acc |= (w & 255) << (8 * (i & 3));
+    if ((i & 3) == 3) { rec[i >> 2] = acc; acc = 0; }
+    return true;
+  };
+  if (h < 128) {
+    st = k1_weight_stream(desc, src, src_end, L, put, &nw);
+  } else {
+    // parse_direct (huffman.rs:92-106): high nibble first
+    nw = (uint32_t)h - 127;
+    for (uint32_t i = 0; i < nw; i++) {
+      const uint8_t b = desc[1 + i / 2];
+      put(i, (i & 1) ? (b & 15) : (b >> 4));
+    }
+  }
+  if (st > 0) return K1_BIG;
+  if (st) return st;
+  if (panic || sum == 0) return ZD_E_REF_PANIC;
+  int p = highbit32(sum);
+  if ((1ull << p) < sum) p++;
+  if (p >= 32) return ZD_E_REF_PANIC;
+  const uint8_t rest = (uint8_t)((1u << p) - sum);
+  if (rest == 0) return ZD_E_REF_PANIC;           // D3
+  const uint32_t manquant = (uint32_t)highbit32(rest) + 1;
+  if (maxw > (uint32_t)p + 1 || manquant > (uint32_t)p + 1) return ZD_E_REF_PANIC;
+  // a complete tree (the codes fill the 2^p prefixes: no hole, every code
+  // placed) of at most K2's LUT bits
+  if (p > K2_LUT_BITS || (uint64_t)sum + (1u << (manquant - 1)) != (1ull << p)) return K1_BIG;
+  rec[nw >> 2] = acc | manquant << (8 * (nw & 3));
+  rec[K1R_HDR] = (nw + 1) | (uint32_t)p << 16;
+  *p_out = p;
+  return 0;
+}
+
+__device__ inline void k1_seq_clear(const CompBlock& C, uint16_t* slot, int from) {
+  for (int k = from; k < 3; k++)
+    if (C.modes[k] == M_FSE) ((uint32_t*)(slot + k * FSE_TAB))[K1R_FSE_HDR] = 0;
+}
+
+// k1_sequences_lane's walk with the FSE-mode tables parsed, not built
+__device__ int k1_sequences_parse(const uint8_t* blk, const CompBlock& C, uint16_t* slot, uint8_t al_out[3],
+                                  uint32_t* bs_off, uint32_t* bs_size, int* sub) {
+  uint32_t pos = C.seq_tables;
+  for (int k = 0; k < 3; k++) {
+    *sub = k;
+    const int mode = C.modes[k];
+    uint16_t* tab = slot + k * FSE_TAB;
+    int st = 0, al = 0;
+    if (mode == M_RLE) {
+      if (pos >= C.size) st = ZD_E_NOT_ENOUGH_BYTES;
+      else { tab[0] = fse_entry(blk[pos], 1); pos++; }   // AL 0: nb 0, baseline 0
+    } else if (mode == M_FSE) {
+      if (pos >= C.size) st = ZD_E_EMPTY_SLICE;
+      else {
+        FwBits fw{blk + pos, C.size - pos, 0};
+        uint8_t a = 0;
+        uint32_t nsym = 0;
+        st = parse_ncount(fw, &a, (int16_t*)tab, &nsym, K1S_SYMS);
+        al = a;
+        pos += fw.bytes_read();
+        if (!st) ((uint32_t*)tab)[K1R_FSE_HDR] = nsym | (uint32_t)al << 16;
+      }
+    } else if (mode == M_PREDEFINED) {
+      al = k == 1 ? 5 : 6;
+    }
+    if (st) {
+      k1_seq_clear(C, slot, k);
+      return st;
+    }
+    if (mode != M_REPEAT) al_out[k] = (uint8_t)al;
+  }
+  *sub = 3;
+  *bs_off = pos;                                  // seq.bitstream = input.slice(input.len()) (sequences.rs:72)
+  *bs_size = pos < C.size ? C.size - pos : 0;
+  return pos >= C.size ? ZD_E_EMPTY_SLICE : 0;
+}
+
+constexpr int K1P_LANES = 64;
+template <int PART>
+__global__ __launch_bounds__(K1P_LANES) void zd_k_tables_parse(const uint8_t* __restrict__ src, uint64_t src_size,
+                                                               const CompBlock* __restrict__ comp, CompState* cstate,
+                                                               FrameState* fstate, const uint32_t* __restrict__ list,
+                                                               uint32_t n_list, uint16_t* luts, uint16_t* fses) {
+  __shared__ K1LaneP lanes[(PART & 1) ? K1P_LANES : 1];
+  const uint32_t li = blockIdx.x * K1P_LANES + threadIdx.x;
+  if (li >= n_list) return;
+  const uint32_t ci = list[li];
+  const CompBlock C = comp[ci];
+  if (C.prebuilt) return;
+  const uint8_t* blk = src + C.src;
+  const bool seq = (PART & 2) && C.nseq > 0 && C.host_stage > PS_SEQ_TABLES;
+  uint16_t* slot = fses + (uint64_t)C.fse_slot * FSE_SLOT;
+  if ((PART & 1) && C.lit_type == LIT_COMPRESSED && C.host_stage > PS_HUF_DESC) {
+    int p = 0;
+    const int st = k1_huffman_parse(blk + C.lit_data, src, src + src_size, lanes[(PART & 1) ? threadIdx.x : 0],
+                                    (uint32_t*)(luts + (uint64_t)C.lut_slot * LUT_ENTRIES), &p);
+    if (st == K1_BIG) {
+      cstate[ci].k1_bigh = 1;                     // zd_k_tables<true> builds this tree
+    } else if (st) {
+      key_min(fstate, C.frame, make_key(PH_PARSE, C.block_in_frame, PS_HUF_DESC, 0, st));
+      if (seq) k1_seq_clear(C, slot, 0);
+      return;                                     // Block::parse stops at the literals section
+    } else {
+      cstate[ci].huf_bits = (uint8_t)p;
+    }
+  }
+  if (seq) {
+    uint8_t al[3] = {0, 0, 0};
+    uint32_t bo = 0, bsz = 0;
+    int sub = 0;
+    const int st = k1_sequences_parse(blk, C, slot, al, &bo, &bsz, &sub);
+    if (st == K1_BIG) {
+      cstate[ci].k1_bigs = 1;                     // zd_k_tables<true> parses and builds these tables
+      return;
+    }
+    for (int k = 0; k < 3; k++)
+      if (C.modes[k] != M_REPEAT && (sub > k || !st)) cstate[ci].al[k] = al[k];
+    cstate[ci].bs_off = bo;
+    cstate[ci].bs_size = bsz;
+    if (st) key_min(fstate, C.frame, make_key(PH_PARSE, C.block_in_frame, PS_SEQ_TABLES, (uint32_t)sub, st));
+  }
+}
+
+// The build pass's scratch of one wave
+struct K1BuildF {                                  // fz_build_fse, a table of <= K1S_SYMS symbols
+  uint64_t lanes[64];
+  uint16_t cum[K1S_SYMS + 4];
+  uint16_t cnt[K1S_SYMS];
+  uint8_t sym[FSE_TAB];
+  int16_t dist[K1S_SYMS];
+};
+struct K1BuildH {
+  uint16_t u[1 << K2_LUT_BITS];                    // the u16 LUT (k1_huffman_lane's entries)
+  uint8_t wts[256];
+  uint8_t sorted[256];                             // the symbols by (weight, symbol): the LUT's order
+};
+template <int PART>
+union K1BuildW {
+  typename std::conditional<(PART & 1) != 0, K1BuildH, uint32_t>::type h;
+  typename std::conditional<(PART & 2) != 0, K1BuildF, uint32_t>::type f;
+};
+
+// from_number_of_bits (huffman.rs:132-175) of a complete tree by a wave: the
+// codes in (width descending, symbol ascending) order fill the 2^p prefixes
+// without a gap, weight v taking 2^(v-1) each, so a counting sort by weight
+// gives the order and each weight's first prefix, and each lane finds its
+// entries' symbols from them.
+__device__ void k1_huffman_wave(uint16_t* slot, K1BuildH& H, int lane) {
+  const uint32_t* rec = (const uint32_t*)slot;
+  const uint32_t hdr = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec[K1R_HDR]);
+  const uint32_t n = hdr & 0xFFFF;
+  const int p = (int)(hdr >> 16);
+  if (n == 0 || n > 256 || p < 1 || p > K2_LUT_BITS) return;
+  ((uint32_t*)H.wts)[lane] = 4u * lane < n ? rec[lane] : 0u;
+  k4_sync();
+  constexpr int VMAX = K2_LUT_BITS + 1;            // weights 1..p (p + 1 never: the tree would be one leaf too many)
+  uint32_t cnt[VMAX + 1], base[VMAX + 1], start[VMAX + 1];
+#pragma unroll
+  for (int v = 0; v <= VMAX; v++) cnt[v] = 0;
+  for (uint32_t c = 0; c < n; c += 64) {
+    const uint32_t wv = c + lane < n ? H.wts[c + lane] : 0u;
+#pragma unroll
+    for (int v = 1; v <= VMAX; v++) cnt[v] += (uint32_t)__popcll(__ballot(wv == (uint32_t)v));
+  }
+  uint32_t b = 0, s0 = 0;
+#pragma unroll
+  for (int v = 1; v <= VMAX; v++) {
+    base[v] = b;
+    start[v] = s0;
+    b += cnt[v];
+    s0 += cnt[v] << (v - 1);
+  }
+  if (s0 != (1u << p)) return;                     // (the parse pass checked it)
+  for (uint32_t c = 0; c < n; c += 64) {
+    const uint32_t wv = c + lane < n ? H.wts[c + lane] : 0u;
+#pragma unroll
+    for (int v = 1; v <= VMAX; v++) {
+      const uint64_t m = __ballot(wv == (uint32_t)v);
+      if (wv == (uint32_t)v) H.sorted[(base[v] + lanes_below(m)) & 255] = (uint8_t)(c + lane);
+      base[v] += (uint32_t)__popcll(m);
+    }
+  }
+  k4_sync();
+  for (uint32_t e = lane; e < (1u << p); e += 64) {
+    uint32_t v = 1, st = 0, first = 0;
+#pragma unroll
+    for (int x = 1; x <= VMAX; x++)                // (base: now past the weight's symbols)
+      if (start[x] <= e) { v = (uint32_t)x; st = start[x]; first = base[x] - cnt[x]; }
+    const uint32_t r = (e - st) >> (v - 1);
+    const uint32_t i = H.sorted[(first + r) & 255];
+    H.u[e] = (uint16_t)(i | lut_field((uint32_t)p + 1 - v, p) << 8);
+  }
+  k4_sync();
+  pr_convert((const lds_u16*)H.u, p, slot, lane);
+}
+
+// The block's sequence tables from the parsed counts (Predefined: the constants)
+__device__ void k1_sequences_wave(const CompBlock& C, uint16_t* slot, K1BuildF& W, int lane) {
+  for (int k = 0; k < 3; k++) {
+    const int mode = C.modes[k];
+    uint16_t* tab = slot + k * FSE_TAB;
+    uint32_t nsym = 0;
+    int al = 0;
+    if (mode == M_FSE) {
+      const uint32_t hdr = (uint32_t)__builtin_amdgcn_readfirstlane((int)((const uint32_t*)tab)[K1R_FSE_HDR]);
+      nsym = hdr & 0xFFFF;
+      al = (int)(hdr >> 16);
+      if (nsym == 0 || nsym > K1S_SYMS || al > FSE_MAX_AL) continue;
+      if ((uint32_t)lane < nsym) W.dist[lane] = (int16_t)tab[lane];
+    } else if (mode == M_PREDEFINED) {
+      const int16_t* d = k == 0 ? c_ll_default : (k == 1 ? c_of_default : c_ml_default);
+      nsym = k == 0 ? 36 : (k == 1 ? 29 : 53);
+      al = k == 1 ? 5 : 6;
+      if ((uint32_t)lane < nsym) W.dist[lane] = d[lane];
+    } else {
+      continue;
+    }
+    k4_sync();
+    fz_build_fse(al, W.dist, nsym, tab, W, lane);
+  }
+}
+
+constexpr int K1B_WAVES = 4;
+template <int PART>
+__global__ __launch_bounds__(64 * K1B_WAVES) void zd_k_tables_build(const CompBlock* __restrict__ comp,
+                                                                    const CompState* cstate,
+                                                                    const uint32_t* __restrict__ list,
+                                                                    uint32_t n_list, uint16_t* luts, uint16_t* fses) {
+  __shared__ __attribute__((aligned(16))) K1BuildW<PART> W[K1B_WAVES];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t li = blockIdx.x * K1B_WAVES + wv;
+  if (li >= n_list) return;                        // whole waves: no workgroup barrier below
+  const uint32_t ci = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[li]);
+  const CompBlock& C = comp[ci];
+  if (C.prebuilt) return;
+  const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane(
+      (int)(cstate[ci].huf_bits | (uint32_t)cstate[ci].k1_bigh << 8 | (uint32_t)cstate[ci].k1_bigs << 16));
+  if constexpr ((PART & 1) != 0) {
+    // (huf_bits: the parse pass took the tree and found no error)
+    if (C.lit_type == LIT_COMPRESSED && C.host_stage > PS_HUF_DESC && (flags & 0xFF) && !(flags & 0xFF00))
+      k1_huffman_wave(luts + (uint64_t)C.lut_slot * LUT_ENTRIES, W[wv].h, lane);
+  }
+  if constexpr ((PART & 2) != 0) {
+    if (C.nseq > 0 && C.host_stage > PS_SEQ_TABLES && !(flags & 0xFF0000))
+      k1_sequences_wave(C, fses + (uint64_t)C.fse_slot * FSE_SLOT, W[wv].f, lane);
+  }
 }
 
 // (measured on C3, within noise: the chain wave at s_setprio 3; eight waves
@@ -5298,8 +5610,27 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
                          fstate, (const uint32_t*)huge, luts, (uint32_t*)(ws + W.deep));
       // K2's pair tables, from the LUTs of maxBits <= 11
       hipLaunchKernelGGL(zd_k_huf_pairs, dim3((a.n_tables + PR_WAVES - 1) / PR_WAVES), dim3(64 * PR_WAVES), 0, st,
-                         comp, (const CompState*)cstate, lt, a.n_tables, luts);
+                         comp, (const CompState*)cstate, lt, a.n_tables, luts, 0u);
     }
+  };
+  // the two passes (ZD_ROUTE_K1_SPLIT), then what they flagged on the lanes
+  auto k1s = [&](auto parse, auto build, auto pass_big, hipStream_t st, uint32_t part) {
+    const uint32_t* lt = (const uint32_t*)(ws + W.list_tables);
+    hipLaunchKernelGGL(parse, dim3((a.n_tables + K1P_LANES - 1) / K1P_LANES), dim3(K1P_LANES), 0, st, a.src,
+                       a.src_size, comp, cstate, fstate, lt, a.n_tables, luts, fses);
+    hipLaunchKernelGGL(build, dim3((a.n_tables + K1B_WAVES - 1) / K1B_WAVES), dim3(64 * K1B_WAVES), 0, st, comp,
+                       (const CompState*)cstate, lt, a.n_tables, luts, fses);
+    hipLaunchKernelGGL(pass_big, dim3((a.n_tables + K1_LANES - 1) / K1_LANES), dim3(K1_LANES), 0, st, a.src,
+                       a.src_size, comp, cstate, fstate, lt, a.n_tables, luts, fses, huge);
+    if (part & 1) {
+      hipLaunchKernelGGL(zd_k_tables_huge, dim3(K1H_GRID), dim3(K1H_LANES), 0, st, a.src, a.src_size, comp, cstate,
+                         fstate, (const uint32_t*)huge, luts, (uint32_t*)(ws + W.deep));
+      hipLaunchKernelGGL(zd_k_huf_pairs, dim3((a.n_tables + PR_WAVES - 1) / PR_WAVES), dim3(64 * PR_WAVES), 0, st,
+                         comp, (const CompState*)cstate, lt, a.n_tables, luts, part == 3 ? 2u : 1u);
+    }
+  };
+  auto k1s_huf = [&](hipStream_t st) {
+    k1s(zd_k_tables_parse<1>, zd_k_tables_build<1>, zd_k_tables<true, 1>, st, 1);
   };
   const bool fz = a.fused && !a.events;
   auto k1seqw = [&](hipStream_t st) {
@@ -5308,7 +5639,15 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
   };
   if (a.n_tables) {
     if (fz) {                                  // the sequence half runs in zd_k_fused
-      k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, s2, true);
+      if (a.k1_split) k1s_huf(s2);
+      else k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, s2, true);
+    } else if (a.k1_split) {                   // the same launch shapes as the lanes' below
+      if (fork || k1f) {
+        k1s_huf(k1f ? a.aux : s2);
+        k1s(zd_k_tables_parse<2>, zd_k_tables_build<2>, zd_k_tables<true, 2>, s, 2);
+      } else {
+        k1s(zd_k_tables_parse<3>, zd_k_tables_build<3>, zd_k_tables<true, 3>, s, 3);
+      }
     } else if (a.k1_seq_waves) {               // few blocks: the sequence half one wave per block
       k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, k1f ? a.aux : s2, true);
       k1seqw(s);

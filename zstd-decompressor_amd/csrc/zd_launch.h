@@ -30,6 +30,7 @@ struct LaunchArgs {
   uint32_t cus = 256;                      // compute units of the device (K4J rounds' grid)
   bool fused = false;                      // K3 + K4 as zd_k_fused, then the redo pass
   bool k1_seq_waves = false;               // K1's sequence half one wave per block (zd_k_tables_seqw)
+  bool k1_split = false;                   // K1 as a parse pass and a build pass (zd_k_tables_parse / _build)
   bool k1_fork = false;                    // no K2 | K3 fork: K1's halves on the two streams (aux, fork, join)
   // optional (zd_plan_set_profiling mode 2): an event pair recorded on
   // `stream` around each launch group that can carry a plan's work -- K0,

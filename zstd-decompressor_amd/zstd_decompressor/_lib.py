@@ -74,6 +74,7 @@ SIGNATURES = {
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "zd_plan_checksums": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "zd_plan_set_profiling": (C.c_int, [_vp, C.c_int]),
+    "zd_plan_k1_fallbacks": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zd_plan_kernel_times": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]),
     "zd_decompress": (C.c_int, [_vp, _sz, _vp, _sz, _szp, C.c_uint32]),
     "zd_plan_decompress": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
@@ -209,4 +210,5 @@ F_NO_FUSE = 32         # K3 then K4 as two launches in few-frame plans (no zd_k_
 F_K1_LANES = 64        # K1's sequence half on serial lanes in plans of <= 16,384 tables
 F_J_ONE_ROUND = 128    # test switch: K4J pointer jumping cut to one round of one hop
 F_SEQ_NO_LATENCY = 256 # K3Q instead of the one-block-per-wave K3L in plans of few blocks
+F_K1_SPLIT = 512       # K1 as a parse pass and a build pass in a plan of any size
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4   # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)
