@@ -74,6 +74,9 @@ extern "C" {
 #define ZD_E_NO_MEMORY       (-95)
 #define ZD_E_NOT_DECODED     (-96) /* frame skipped: an earlier frame failed (FrameIterator stops, frame.rs:94-99) */
 #define ZD_E_COMM            (-97) /* an RCCL call failed, or RCCL is not loadable */
+#define ZD_E_DICT_CORRUPTED  (-98) /* zd_dict_create: a formatted dictionary truncated before its content, with
+                                      a repeat offset of 0 or past the content, or without content */
+#define ZD_E_DICT_MISMATCH   (-99) /* a frame names a Dictionary_ID other than the plan's dictionary's */
 
 /* Device workspaces of destroyed plans are kept for reuse by later plans of
  * the process (bounded by ZD_WS_CACHE_MB, default 8 GiB; 0 disables it).
@@ -327,6 +330,60 @@ int zd_plan_frame_outputs(const zd_plan* plan, int32_t* status, uint64_t* offset
  * stream).  Mirrors the CLI (src/main.rs:43-58) minus the UTF-8 step. */
 int zd_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap,
                   size_t* out_len, uint32_t flags);
+
+/* ------------------------------------------------------------------ */
+/* Dictionaries (RFC 8878 5; beyond the reference, which parses a       */
+/* frame's Dictionary_ID and ignores it, frame.rs:143-152).             */
+/* ------------------------------------------------------------------ */
+typedef struct zd_dict zd_dict;
+
+/* A dictionary from host bytes, on the current device.  A formatted
+ * dictionary starts with the magic number 0xEC30A437: a 4-byte ID, the Huffman
+ * tree description, the FSE descriptions of the offset, match length and
+ * literal length tables, three 4-byte little-endian repeat offsets, then the
+ * content.  Any other byte string is a raw-content dictionary: ID 0, no
+ * tables, repeat offsets 1, 4, 8, the whole string content.  The content is
+ * copied into device memory the object owns and the four tables are built on
+ * the GPU once (zd_k_dict_tables); the call synchronises.
+ *   ZD_E_DICT_CORRUPTED  truncated anywhere before the content; a repeat
+ *                        offset of 0 or larger than the content; no content
+ *   the table's own code (ZD_E_CORRUPTED_TABLE, ZD_E_LARGE_ACCURACY_LOG, ...)
+ *                        when a description fails as it would in a block
+ *   ZD_E_OUT_OF_DOMAIN   a Huffman tree deeper than 11 bits (libzstd writes
+ *                        none), or more than ZD_DICT_MAX_CONTENT bytes of content */
+#define ZD_DICT_MAX_CONTENT (1ull << 30)
+int  zd_dict_create(const uint8_t* dict, size_t n, zd_dict** out);
+/* Legal before the plans made with it are destroyed: they share ownership. */
+void zd_dict_destroy(zd_dict* d);
+/* raw_content: 1 for a raw-content dictionary.  Any pointer may be NULL. */
+int  zd_dict_info(const zd_dict* d, uint32_t* dict_id, uint64_t* content_size,
+                  uint64_t rep[3], int* raw_content);
+/* zd_plan_create with a dictionary (dict == NULL: zd_plan_create).  Every
+ * zstd frame of the plan decodes with it: its tables stand for the block
+ * before the frame's first (Treeless literals, Repeat modes), its repeat
+ * offsets are the frame's first, and a match may reach into its content
+ * however far the frame has advanced (no window check, as everywhere here:
+ * DESIGN.md D4); an offset larger than content size + position is
+ * ZD_E_IMPOSSIBLE_VALUE.  A frame that names a non-zero Dictionary_ID other
+ * than the dictionary's gets ZD_E_DICT_MISMATCH and the plan stops there like
+ * at any failing frame; a frame without an ID decodes with the dictionary,
+ * as in libzstd.  One quirk of the reference is not kept in these plans, whose
+ * yardstick is libzstd: a Raw literals section of 0 bytes (a record found
+ * wholly in the dictionary) is accepted, where the reference's zero-length
+ * slice is an EmptySliceError.  The output holds the frames' own bytes only, contiguous;
+ * every zd_plan_* call and zd_decode_async work as on any plan (no host copy
+ * or allocation per launch; capturable).  A dictionary made on another
+ * device: ZD_E_INVALID_ARG.
+ * Limits: dictionary plans run on the streaming executor only -- never the
+ * fused kernel, K4F or K4J, ZD_F_BLOCK_PARALLEL is ignored and
+ * zd_plan_info.executors is 0; a frame whose dictionary content plus
+ * capacity passes the streaming executor's int32 positions is
+ * ZD_E_OUT_OF_DOMAIN.  zd_plan_create_device, the sharded calls and zd_context
+ * take no dictionary. */
+int  zd_plan_create_dict(const uint8_t* src, size_t n, uint32_t flags, const zd_dict* dict, zd_plan** out);
+/* zd_decompress with a dictionary. */
+int  zd_decompress_dict(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len,
+                        uint32_t flags, const zd_dict* dict);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: frame-range sharding + RCCL gather.      */

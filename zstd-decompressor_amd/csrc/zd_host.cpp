@@ -16,6 +16,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -52,10 +53,40 @@ struct VecSink {
 }  // namespace
 
 // ===========================================================================
+// Dictionary (zd_dict_create): the content and the four tables on the device,
+// shared by the zd_dict handle and every plan made with it.
+// ===========================================================================
+namespace {
+constexpr uint32_t DICT_MAGIC = 0xEC30A437u;
+constexpr size_t DICT_PAD = 16;          // readable bytes on both sides of the content (K4's 16-byte pieces)
+struct DictData {
+  int dev = -1;
+  uint8_t* d_buf = nullptr;              // DICT_PAD zero bytes, the dictionary's bytes, zero bytes to the end
+  const uint8_t* d_content = nullptr;    // inside d_buf
+  uint64_t content = 0;
+  uint32_t id = 0;
+  bool raw = true;
+  uint64_t rep[3] = {1, 4, 8};
+  uint16_t* d_lut = nullptr;             // formatted: one LUT slot (the pair table) and one FSE slot
+  uint16_t* d_fse = nullptr;
+  uint8_t huf_bits = 0, al[3] = {0, 0, 0};
+  ~DictData() {
+    if (d_buf) (void)hipFree(d_buf);
+    if (d_lut) (void)hipFree(d_lut);
+    if (d_fse) (void)hipFree(d_fse);
+  }
+};
+}  // namespace
+struct zd_dict {
+  std::shared_ptr<DictData> p;
+};
+
+// ===========================================================================
 // Plan
 // ===========================================================================
 struct zd_plan {
   uint32_t flags = 0;
+  std::shared_ptr<DictData> dict;       // a dictionary plan (zd_plan_create_dict): kept alive by the plan
   std::vector<HostPart> parts;          // the host walk's frames, in input order
   std::vector<size_t> part_f0;          // plan frame index of each part's first frame
   size_t nframes = 0;
@@ -370,10 +401,13 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   for (const HostPart& hp : P->parts)
     if (!hp.frames.empty()) { X.cap0_frame = hp.frames.data(); break; }
   X.flags = P->flags;
+  X.dict = P->dict != nullptr;
+  X.dict_id = P->dict ? P->dict->id : 0;
   RouteIn in{};
   in.cus = (uint32_t)(k3_slots() / 64);
   in.nframes = P->nframes;
-  in.context = out_len0 != 0 || P->has_prebuilt;
+  // (a dictionary plan routes like a context plan: the streaming executor only)
+  in.context = out_len0 != 0 || P->has_prebuilt || X.dict;
   in.flags = P->flags;
   in.single_block_frames = single;
   const Route r = route_plan(in);
@@ -389,6 +423,7 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   X.k4j_mode = k4j_mode_of(P->flags);
   X.k4j_min = P->nframes <= K4J_FEW_FRAMES ? K4J_MIN_BLOCKS_FEW : K4J_MIN_BLOCKS;
   X.k4j_auto = X.k4j_mode < 0 && out_len0 == 0 && j_candidates > 0 && j_candidates <= K4J_MAX_FRAMES;
+  if (X.dict) { X.k4f_on = false; X.k4j_auto = false; X.k4j_mode = 0; }
   return X;
 }
 
@@ -460,7 +495,7 @@ void plan_info(zd_plan* P, const PlanCounts& T) {
   zd_plan_info& I = P->info;
   I.nframes = T.frames;
   I.nblocks = T.blocks;
-  I.ncompressed = T.comps;
+  I.ncompressed = T.comps - ((P->dict && !P->dict->raw) ? 1 : 0);   // (not the dictionary's prebuilt comp)
   I.out_bytes = T.out;
   I.out_exact = T.exact();
   I.workspace_bytes = P->W.total;
@@ -494,6 +529,10 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
 
   const size_t np = P->parts.size();
   std::vector<PlanCounts> cnt(np + 1);
+  // a formatted dictionary's tables: the plan-level prebuilt comp 0 with LUT
+  // slot 0 and FSE slot 0, before every frame's (X.prev_huf / X.prev_tab name it)
+  const bool dict_comp = P->dict && !P->dict->raw;
+  if (dict_comp) cnt[0].comps = cnt[0].luts = cnt[0].fses = 1;
   const Sink none{};
   run_parts(np, [&](size_t k) {
     const HostPart& hp = P->parts[k];
@@ -569,6 +608,19 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
     PlanCounts c = cnt[k];
     for (const HostFrame& hf : hp.frames) plan_frame<true, JMax>(X, hf, hp.blocks.data(), c, S, &jm[k]);
   });
+  if (dict_comp) {
+    CompBlock pb{};
+    pb.lit_type = LIT_COMPRESSED;
+    pb.host_stage = PS_ALL;
+    pb.nseq = 1;
+    pb.modes[0] = pb.modes[1] = pb.modes[2] = M_FSE;
+    pb.prebuilt = 1;
+    pb.huf_src = 0;
+    pb.tab_src[0] = pb.tab_src[1] = pb.tab_src[2] = 0;
+    pb.lut_slot = 0;
+    pb.fse_slot = 0;
+    S.comps[0] = pb;
+  }
   uint64_t j_maxseq = 0;
   for (const JMax& m : jm) j_maxseq = std::max(j_maxseq, m.m);
   carve_tail(P, W, T, o, T.jwords, T.jpieces, j_maxseq);
@@ -745,11 +797,11 @@ void aux_give(zd_plan* P) {
 // Frames from in (FrameIterator::next, frame.rs:94-99) into `part` until the
 // input ends, a frame starting at or past `stop` comes up, or one fails (kept,
 // with its status).
-int index_frames(const uint8_t* src, Bytes& in, size_t stop, HostPart& part) {
+int index_frames(const uint8_t* src, Bytes& in, size_t stop, HostPart& part, bool rfc_empty_lits) {
   while (in.n && (size_t)(in.p - src) < stop) {
     HostFrame hf;
     VecSink sink{part.blocks};
-    int r = index_frame(src, in, &hf, sink);
+    int r = index_frame(src, in, &hf, sink, rfc_empty_lits);
     part.frames.push_back(hf);
     if (r) return r;
   }
@@ -788,6 +840,7 @@ int plan_index(zd_plan* P, const uint8_t* src, size_t n) {
   static const char* wt = getenv("ZD_WALK_THREADS");   // experiments
   const unsigned hw = wt ? (unsigned)std::max(1, atoi(wt)) : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   const size_t T = n >= PAR_INDEX_MIN_BYTES ? std::min<size_t>(hw, n >> 20) : 1;
+  const bool rfc_empty_lits = P->dict != nullptr;   // (zd_walk.h parse_compressed)
   std::vector<HostPart> part(T);
   std::vector<int> st(T, 0);
   std::vector<size_t> end(T, 0), cut(T + 1);
@@ -808,7 +861,7 @@ int plan_index(zd_plan* P, const uint8_t* src, size_t n) {
       }
       part[k].blocks.reserve((cut[k + 1] - cut[k]) / (16u << 10) + 16);
       Bytes in{src + p, n - p};
-      st[k] = index_frames(src, in, cut[k + 1], part[k]);
+      st[k] = index_frames(src, in, cut[k + 1], part[k], rfc_empty_lits);
       end[k] = (size_t)(in.p - src);
       // a candidate that fails at once was a magic inside data: look further
       if (k && st[k] && part[k].frames.size() == 1) {
@@ -849,7 +902,7 @@ int plan_index(zd_plan* P, const uint8_t* src, size_t n) {
     while (in.n) {
       HostFrame hf;
       VecSink sink{tail.blocks};
-      const int r = index_frame(src, in, &hf, sink);
+      const int r = index_frame(src, in, &hf, sink, rfc_empty_lits);
       tail.frames.push_back(hf);
       const size_t p = (size_t)(in.p - src);
       serial += p - cur;
@@ -1385,6 +1438,8 @@ const char* zd_status_name(int s) {
     case ZD_E_NO_MEMORY: return "NoMemory";
     case ZD_E_NOT_DECODED: return "NotDecoded";
     case ZD_E_COMM: return "CommError";
+    case ZD_E_DICT_CORRUPTED: return "DictionaryCorrupted";
+    case ZD_E_DICT_MISMATCH: return "DictionaryMismatch";
     default: return "Unknown";
   }
 }
@@ -1470,11 +1525,12 @@ extern "C" {
 // zd_plan_create / zd_plan_create_device: the walk (host or device), then
 // the descriptors, the workspace and the upload.
 static int plan_create(const uint8_t* src, const uint8_t* d_src, size_t n, uint32_t flags, hipStream_t s,
-                       zd_plan** out, uint64_t cap0) {
+                       zd_plan** out, uint64_t cap0, const std::shared_ptr<DictData>& dict = nullptr) {
   zd_plan* P = new (std::nothrow) zd_plan();
   if (!P) return ZD_E_NO_MEMORY;
   P->flags = flags;
   P->cap0 = cap0;
+  P->dict = dict;
   const auto t0 = std::chrono::steady_clock::now();
   if (d_src) {
     if (int r = plan_index_dev(P, d_src, n, s)) { zd_plan_destroy(P); return r; }
@@ -1484,7 +1540,16 @@ static int plan_create(const uint8_t* src, const uint8_t* d_src, size_t n, uint3
   const auto ti = std::chrono::steady_clock::now();
   int32_t none[3] = {-1, -1, -1};
   uint64_t rep0[3] = {1, 4, 8};
-  if (!P->dev_built)
+  if (dict) {
+    // the dictionary's tables are the prebuilt comp 0 (a raw-content
+    // dictionary has none), its repeat offsets every frame's first, and its
+    // content the positions before every frame
+    const int32_t pre[3] = {0, 0, 0};
+    if (int r = build_plan(P, dict->raw ? -1 : 0, dict->raw ? none : pre, dict->content, dict->rep, 0, true)) {
+      zd_plan_destroy(P);
+      return r;
+    }
+  } else if (!P->dev_built)
     if (int r = build_plan(P, -1, none, 0, rep0, 0, true)) { zd_plan_destroy(P); return r; }
   P->info.src_bytes = n;
   const auto t1 = std::chrono::steady_clock::now();
@@ -1494,6 +1559,19 @@ static int plan_create(const uint8_t* src, const uint8_t* d_src, size_t n, uint3
             std::chrono::duration<double, std::milli>(ti - t0).count(),
             std::chrono::duration<double, std::milli>(t1 - ti).count());
   int r = P->dev_built ? upload_staging(P) : upload_plan(P);
+  if (!r && dict && !dict->raw) {
+    // the prebuilt comp's slots and state, once: zd_k_reset leaves comp 0's
+    // state alone (launch_reset keep_comps), no launch writes the slots
+    CompState pcs{};
+    pcs.huf_bits = dict->huf_bits;
+    for (int k = 0; k < 3; k++) pcs.al[k] = dict->al[k];
+    if (hipMemcpy(P->d_ws + P->W.luts, dict->d_lut, LUT_ENTRIES * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipMemcpy(P->d_ws + P->W.fses, dict->d_fse, FSE_SLOT * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipMemcpy(P->d_ws + P->W.comp_state, &pcs, sizeof pcs, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      r = ZD_E_HIP;
+    }
+  }
   const auto tu = std::chrono::steady_clock::now();
   // the second stream and its events (K2 beside K3) exist
   // from here on, so zd_decode_async creates nothing
@@ -1614,7 +1692,8 @@ int zd_decode_async(zd_plan* P, const uint8_t* d_src, uint8_t* d_dst, size_t dst
   // deep pool counters, K4J's round counters and done flags; ZD_RESET_COPIES
   // builds keep the six copy / fill launches it replaced)
 #ifndef ZD_RESET_COPIES
-  HIPCHK(launch_reset(P->d_ws, P->W, P->n_frames, P->n_comps, P->n_jframes != 0, P->j_pieces, s));
+  HIPCHK(launch_reset(P->d_ws, P->W, P->n_frames, P->n_comps, P->n_jframes != 0, P->j_pieces, s,
+                      (P->dict && !P->dict->raw) ? 1u : 0u));
 #else
   HIPCHK(hipMemcpyAsync(P->d_ws + P->W.frame_state, P->d_ws + P->W.frame_state0,
                         P->n_frames * sizeof(FrameState), hipMemcpyDeviceToDevice, s));
@@ -1659,6 +1738,7 @@ int zd_decode_async(zd_plan* P, const uint8_t* d_src, uint8_t* d_dst, size_t dst
   a.j_hops2 = one_round ? 1u : hops2_env ? (uint32_t)std::max(1, atoi(hops2_env)) : 12u;
   a.cus = (uint32_t)(k3_slots() / 64);
   a.stream = s;
+  if (P->dict) a.dict = P->dict->d_content;
   // K3 as four lanes per block (K3Q, default): C3 (763 blocks) 2.89 -> 2.31
   // ms, a forked 8,192-block plan 4.24 -> 2.48, full C4 13.88 -> 13.80; the
   // plan flag ZD_F_SEQ_ONE_LANE keeps the one-lane chain (same records)
@@ -1910,7 +1990,9 @@ int zd::decode_resident(zd_plan* P, const uint8_t* src, size_t n, const uint8_t*
     if (cur->limit_stage == LS_CAPACITY) {
       // past K4J's 32 GiB, or with K4J forced off the streaming K4's int32
       // positions (plan_frame keys a larger frame out of domain): stop
-      const uint64_t lim = k4j_mode_of(flags) == 0 ? K4_MAX_FRAME_OUT : K4J_MAX_FRAME_OUT;
+      // (a dictionary plan: the streaming K4's, less the content before the frame)
+      const uint64_t lim = cur->dict ? K4_MAX_FRAME_OUT - cur->dict->content
+                                     : k4j_mode_of(flags) == 0 ? K4_MAX_FRAME_OUT : K4J_MAX_FRAME_OUT;
       if (old_cap >= lim) break;
       cap0 = std::min<uint64_t>(lim, std::max<uint64_t>(4 * old_cap, old_cap + (1u << 20)));
     } else {
@@ -1920,7 +2002,7 @@ int zd::decode_resident(zd_plan* P, const uint8_t* src, size_t n, const uint8_t*
     if (!cur->frames_ready()) { st = ZD_E_HIP; break; }
     const size_t at = base + (size_t)cur->frame(f).d.src_offset;
     zd_plan* Q = nullptr;
-    const int r = plan_create(src + at, nullptr, n - at, flags, nullptr, &Q, cap0);
+    const int r = plan_create(src + at, nullptr, n - at, flags, nullptr, &Q, cap0, cur->dict);
     if (r) { st = r; break; }
     if (replans) (*replans)++;
     const uint64_t qob = std::max<uint64_t>(Q->info.out_bytes, 16);
@@ -1999,6 +2081,96 @@ int zd_plan_frame_outputs(const zd_plan* P, int32_t* status, uint64_t* offset, u
 int zd_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, uint32_t flags) {
   zd_plan* P = nullptr;
   int r = zd_plan_create(src, n, flags, &P);
+  if (r) return r;
+  r = zd_plan_decompress(P, src, n, dst, cap, out_len);
+  zd_plan_destroy(P);
+  return r;
+}
+
+// ---------------------------------------------------------------------------
+// Dictionaries
+// ---------------------------------------------------------------------------
+int zd_dict_create(const uint8_t* dict, size_t n, zd_dict** out) {
+  if (!dict || !n || !out) return ZD_E_INVALID_ARG;
+  auto rd32 = [&](size_t at) {
+    return (uint32_t)dict[at] | (uint32_t)dict[at + 1] << 8 | (uint32_t)dict[at + 2] << 16 | (uint32_t)dict[at + 3] << 24;
+  };
+  const bool formatted = n >= 4 && rd32(0) == DICT_MAGIC;
+  if (formatted && n < 8) return ZD_E_DICT_CORRUPTED;
+  // (a formatted dictionary's content is smaller than n: one bound for both)
+  if (n > ZD_DICT_MAX_CONTENT + (formatted ? (64u << 10) : 0)) return ZD_E_OUT_OF_DOMAIN;
+  std::shared_ptr<DictData> D(new (std::nothrow) DictData());
+  zd_dict* h = new (std::nothrow) zd_dict();
+  if (!D || !h) { delete h; return ZD_E_NO_MEMORY; }
+  std::unique_ptr<zd_dict> hold(h);
+  HIPCHK(hipGetDevice(&D->dev));
+  const size_t bytes = DICT_PAD + n + 2 * DICT_PAD;
+  HIPCHK(hipMalloc(&D->d_buf, bytes));
+  HIPCHK(hipMemset(D->d_buf, 0, DICT_PAD));
+  HIPCHK(hipMemset(D->d_buf + DICT_PAD + n, 0, 2 * DICT_PAD));
+  HIPCHK(hipMemcpy(D->d_buf + DICT_PAD, dict, n, hipMemcpyHostToDevice));
+  if (!formatted) {
+    D->d_content = D->d_buf + DICT_PAD;
+    D->content = n;
+  } else {
+    D->raw = false;
+    D->id = rd32(4);
+    HIPCHK(hipMalloc(&D->d_lut, LUT_ENTRIES * 2));
+    HIPCHK(hipMalloc(&D->d_fse, FSE_SLOT * 2));
+    HIPCHK(hipMemset(D->d_lut, 0, LUT_ENTRIES * 2));
+    HIPCHK(hipMemset(D->d_fse, 0, FSE_SLOT * 2));
+    DictTables* d_res = nullptr;
+    HIPCHK(hipMalloc(&d_res, sizeof(DictTables)));
+    DictTables res{};
+    hipError_t e = launch_dict_tables(D->d_buf + DICT_PAD, (uint32_t)n, D->d_lut, D->d_fse, d_res, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipMemcpy(&res, d_res, sizeof res, hipMemcpyDeviceToHost);
+    (void)hipFree(d_res);
+    HIPCHK(e);
+    if (res.status) return res.status;
+    // the repeat offsets, then the content
+    if ((uint64_t)res.rep_off + 12 > n) return ZD_E_DICT_CORRUPTED;
+    D->content = n - res.rep_off - 12;
+    if (!D->content) return ZD_E_DICT_CORRUPTED;
+    if (D->content > ZD_DICT_MAX_CONTENT) return ZD_E_OUT_OF_DOMAIN;
+    for (int k = 0; k < 3; k++) {
+      D->rep[k] = rd32(res.rep_off + 4 * (size_t)k);
+      if (!D->rep[k] || D->rep[k] > D->content) return ZD_E_DICT_CORRUPTED;
+    }
+    D->d_content = D->d_buf + DICT_PAD + res.rep_off + 12;
+    D->huf_bits = (uint8_t)res.huf_bits;
+    for (int k = 0; k < 3; k++) D->al[k] = res.al[k];
+  }
+  h->p = std::move(D);
+  *out = hold.release();
+  return ZD_OK;
+}
+
+void zd_dict_destroy(zd_dict* d) { delete d; }
+
+int zd_dict_info(const zd_dict* d, uint32_t* dict_id, uint64_t* content_size, uint64_t rep[3], int* raw_content) {
+  if (!d || !d->p) return ZD_E_INVALID_ARG;
+  if (dict_id) *dict_id = d->p->id;
+  if (content_size) *content_size = d->p->content;
+  if (rep) for (int k = 0; k < 3; k++) rep[k] = d->p->rep[k];
+  if (raw_content) *raw_content = d->p->raw ? 1 : 0;
+  return ZD_OK;
+}
+
+int zd_plan_create_dict(const uint8_t* src, size_t n, uint32_t flags, const zd_dict* dict, zd_plan** out) {
+  if (!out || (!src && n)) return ZD_E_INVALID_ARG;
+  if (!dict) return plan_create(src, nullptr, n, flags, nullptr, out, 0);
+  if (!dict->p) return ZD_E_INVALID_ARG;
+  int dev = -1;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev != dict->p->dev) return ZD_E_INVALID_ARG;
+  return plan_create(src, nullptr, n, flags, nullptr, out, 0, dict->p);
+}
+
+int zd_decompress_dict(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, uint32_t flags,
+                       const zd_dict* dict) {
+  zd_plan* P = nullptr;
+  int r = zd_plan_create_dict(src, n, flags, dict, &P);
   if (r) return r;
   r = zd_plan_decompress(P, src, n, dst, cap, out_len);
   zd_plan_destroy(P);

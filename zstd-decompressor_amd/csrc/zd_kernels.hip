@@ -1129,6 +1129,79 @@ __global__ __launch_bounds__(64 * PR_WAVES) void zd_k_huf_pairs(const CompBlock*
   pr_convert((const lds_u16*)u[wv], p, slot, lane);
 }
 
+// zd_k_dict_tables (zd_dict_create, once per dictionary): the entropy section
+// of a formatted dictionary d[0, n) (RFC 8878 5: magic, ID, then from byte 8
+// the Huffman tree description, the FSE descriptions of the offset, match
+// length and literal length tables -- a block has them in LL, OF, ML order --
+// and three repeat offsets) into one LUT slot and one FSE slot, in the state
+// K2 and K3 expect of a prebuilt comp: the slot holds the pair table
+// (zd_k_huf_pairs skips prebuilt comps), the FSE slot LL | OF | ML.  One
+// workgroup of one wave: lane 0 walks the descriptions with K1's code, the
+// wave converts the LUT.  A description that runs off the end of d is
+// ZD_E_DICT_CORRUPTED, any other failure keeps the code a block would get; a
+// tree deeper than K2's LUT (libzstd writes none) is ZD_E_OUT_OF_DOMAIN.
+__global__ __launch_bounds__(64) void zd_k_dict_tables(const uint8_t* __restrict__ d, uint32_t n, uint16_t* lut,
+                                                       uint16_t* fse, DictTables* res) {
+  __shared__ K1Lane L;
+  __shared__ __attribute__((aligned(16))) uint16_t u[1 << K2_LUT_BITS];
+  __shared__ int s_st;
+  // (pr_convert is one outlined function, specialised by what all its callers
+  // pass: p as a byte and the lane masked, as K1's callers have them, keep its
+  // code what it was)
+  __shared__ uint8_t s_p;
+  const int lane = threadIdx.x & 63;
+  if (lane == 0) {
+    int st = 0, p = 0;
+    uint32_t pos = 8;
+    uint8_t al[3] = {0, 0, 0};
+    if (n < 9) {
+      st = ZD_E_DICT_CORRUPTED;
+    } else {
+      const uint32_t h = d[8];
+      const uint32_t sz = 1 + (h < 128 ? h : (h - 127 + 1) / 2);
+      if (pos + sz > n) {
+        st = ZD_E_DICT_CORRUPTED;
+      } else {
+        st = k1_huffman_lane(d + 8, d, d + n, L, lut, &p);
+        if (st > 0 || (!st && p > K2_LUT_BITS)) st = ZD_E_OUT_OF_DOMAIN;   // (K1_HUGE: more than 255 weights)
+        pos += sz;
+      }
+    }
+    const int order[3] = {1, 2, 0};                 // OF, ML, LL
+    for (int t = 0; t < 3 && !st; t++) {
+      const int k = order[t];
+      if (pos >= n) { st = ZD_E_DICT_CORRUPTED; break; }
+      FwBits fw{d + pos, n - pos, 0};
+      uint8_t a = 0;
+      uint32_t nsym = 0;
+      st = parse_ncount(fw, &a, L.dist, &nsym, K1Lane::SYMS);
+      if (!st) st = build_fse(a, L.dist, nsym, fse + k * FSE_TAB, L.sym, L.next);
+      if (st == ZD_E_NOT_ENOUGH_BITS) st = ZD_E_DICT_CORRUPTED;   // the description runs off the dictionary's end
+      al[k] = a;
+      pos += fw.bytes_read();
+    }
+    res->status = st;
+    res->rep_off = pos;
+    res->huf_bits = (uint32_t)p;
+    for (int k = 0; k < 3; k++) res->al[k] = al[k];
+    res->pad = 0;
+    s_st = st;
+    s_p = (uint8_t)(st ? 0 : p);
+  }
+  __threadfence();
+  __syncthreads();
+  if (s_st) return;
+  const int p = s_p;
+  {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const int n16 = (1 << p) / 8;
+    if (n16 == 0) { if (lane < (1 << p)) u[lane] = lut[lane]; }
+    else for (int e = lane; e < n16; e += 64) ((u32x4*)u)[e] = ((const u32x4*)lut)[e];
+  }
+  __syncthreads();
+  pr_convert((const lds_u16*)u, p, lut, lane);
+}
+
 // One Huffman stream of a tree of maxBits p <= 11 from its pair table (LDS,
 // or HBM for a workgroup with a deeper tree; huffman.rs:205-218 on a
 // BackwardBitParser, parsing.rs:191-259).  Fast path while at least
@@ -2642,11 +2715,17 @@ __device__ inline void k4_sync() {
 
 // The window geometry: C bytes, W of history kept by a slide, B of room
 // kept for a batch.
-template <int C_, int W_, int B_>
+// DICT (zd_k_execute_dict): the positions [0, lo) before the frame are the
+// dictionary's content (dict[p]), the frame's own bytes start at lo and `out`
+// is moved down by lo, so out + p is the byte's address for every p >= lo.
+template <int C_, int W_, int B_, bool DICT_ = false>
 struct K4W {
   static constexpr int C = C_, W = W_, B = B_;
+  static constexpr bool DICT = DICT_;
   l_u8* buf;
   uint8_t* out;            // frame output (frame position 0)
+  const uint8_t* dict;     // DICT: dictionary content (frame position 0), 16 readable bytes on both sides
+  int32_t lo;              // DICT: frame position of the frame's first own byte (the content size)
   int32_t a0;              // frame position of the first 16-byte aligned HBM address (0..15)
   int32_t hs;              // frame position of buf[0]; hs = a0 (mod 16), may be < 0
   int32_t pos;             // decoded length
@@ -2657,7 +2736,23 @@ struct K4W {
   __device__ inline int32_t space() const { return C - (pos - hs); }
   __device__ inline int32_t alignd(int32_t p) const { return ((p - a0) & ~15) + a0; }
   // 16 bytes of frame output at p (p >= 0): LDS when inside the window, else HBM
-  __device__ inline u32x4 src16(int32_t p) const { return p >= hs ? lds16(at(p)) : ldg16_src(out + (uint32_t)p); }
+  __device__ inline u32x4 src16(int32_t p) const {
+    if constexpr (DICT) {
+      if (p >= hs) return lds16(at(p));
+      if (p + 16 <= lo) return ldg16_src(dict + p);
+      if (p >= lo) return ldg16_src(out + (uint32_t)p);
+      // the piece spans the dictionary's last bytes and the frame's first,
+      // which are not neighbours in memory: byte by byte (rare)
+      uint32_t w[4] = {0, 0, 0, 0};
+      for (int b = 0; b < 16; b++) w[b >> 2] |= (uint32_t)byte_before(p + b) << (8 * (b & 3));
+      return (u32x4){w[0], w[1], w[2], w[3]};
+    }
+    return p >= hs ? lds16(at(p)) : ldg16_src(out + (uint32_t)p);
+  }
+  // DICT: one byte at p (p < hs + 16), wherever it lives
+  __device__ inline uint8_t byte_before(int32_t p) const {
+    return p < lo ? dict[p] : (p >= hs ? *at(p) : out[p]);
+  }
 };
 typedef K4W<K4_C, K4_W, K4_B> K4;
 
@@ -2667,10 +2762,10 @@ __device__ __attribute__((always_inline)) inline void k4_flush(WX& X, bool final
   const int32_t A = X.alignd(X.fl), E = X.alignd(X.pos);
   for (int32_t c = A + 16 * X.lane; c < E; c += 1024) {
     const u32x4 v = lds16(X.at(c));
-    if (c >= 0) {
+    if (c >= (WX::DICT ? X.lo : 0)) {
       *(g_u32x4*)(X.out + c) = v;
     } else {                                   // the frame's head chunk: only its own bytes
-      for (int32_t b = 0; b < c + 16; b++) X.out[b] = *X.at(b);
+      for (int32_t b = WX::DICT ? X.lo : 0; b < c + 16; b++) X.out[b] = *X.at(b);
     }
   }
   if (final) {
@@ -2754,7 +2849,8 @@ __device__ __attribute__((always_inline)) inline bool k4_emit_match(WX& X, l_u8*
       } else {                                 // the piece wraps at the period
         for (uint32_t b = 0; b < m; b++) {
           const int32_t p = q - (int32_t)off + (int32_t)((j + b) % off);
-          *X.at(X.pos + x + b) = p >= X.hs ? *X.at(p) : __builtin_nontemporal_load(X.out + p);
+          if constexpr (WX::DICT) *X.at(X.pos + x + b) = X.byte_before(p);
+          else *X.at(X.pos + x + b) = p >= X.hs ? *X.at(p) : __builtin_nontemporal_load(X.out + p);
         }
       }
     }
@@ -2880,7 +2976,7 @@ __device__ inline bool k4f_wait_recs(const K4Fuse& z, uint32_t rec_end) {
   return false;
 }
 
-template <bool FZ>
+template <bool FZ, bool DICT = false>
 __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __restrict__ src, uint8_t* outbase,
                                                    const FrameDesc* __restrict__ frames, FrameState* fstate,
                                                    const BlockRec* __restrict__ blocks,
@@ -2890,7 +2986,9 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
                                                    const uint64_t* __restrict__ seqs,
                                                    const uint16_t* __restrict__ fses, uint32_t f_begin,
                                                    uint32_t f_end, uint32_t f_step, const uint8_t* __restrict__ redo,
-                                                   const K4Lds& M, const K4Fuse* fz, uint8_t* redo_out) {
+                                                   const K4Lds& M, const K4Fuse* fz, uint8_t* redo_out,
+                                                   const uint8_t* __restrict__ dict = nullptr) {
+  static_assert(!DICT || (ZD_K4_OVS && !FZ), "the dictionary variant: pass 0's merged chunks, the streaming kernel");
   l_u8* const win = M.win;
   l_u8* const pat = M.pat;
   l_u8* const stg = M.stg;
@@ -2924,19 +3022,35 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
   const uint64_t key0 = S->key;
   if (key0 != KEY_NONE && key_phase(key0) == PH_PARSE) continue;
 
-  K4 X;
+  K4W<K4_C, K4_W, K4_B, DICT> X;
   X.buf = (l_u8*)win;
   X.out = outbase + F.out;
+  // (a dictionary plan: F.out and F.out_cap are the frame's own region, the
+  // positions below F.out_len0 the dictionary; the planner keeps the sum
+  // below K4_MAX_FRAME_OUT)
+  const uint64_t cap64 = DICT ? F.out_cap + F.out_len0 : F.out_cap;
+  if constexpr (DICT) {
+    X.dict = dict;
+    X.lo = (int32_t)F.out_len0;
+    X.out -= F.out_len0;
+  }
   X.a0 = (int32_t)((16 - ((uintptr_t)X.out & 15)) & 15);
   X.lane = lane;
   X.pos = (int32_t)(F.out_len0 + F.skip_bytes);    // K0 wrote the leading raw/RLE blocks
   X.fl = X.pos;
-  X.cap = (int32_t)(F.out_cap < 0x7FFFFFF0ull ? F.out_cap : 0x7FFFFFF0ull);
+  X.cap = (int32_t)(cap64 < 0x7FFFFFF0ull ? cap64 : 0x7FFFFFF0ull);
   {
     // window start: aligned, at most K4_W bytes back (context API: the
     // existing output's tail comes back from HBM)
     X.hs = X.alignd(X.pos > K4_W ? X.pos - K4_W : 0);
-    for (int32_t p = (X.hs > 0 ? X.hs : 0) + lane; p < X.pos; p += 64) *X.at(p) = X.out[p];
+    if constexpr (DICT) {
+      // the dictionary's tail in 16-byte pieces (hs >= -15 and the last piece
+      // ends below lo + 16: the buffer's padding), then K0's bytes
+      for (int32_t p = X.hs + 16 * lane; p < X.lo; p += 1024) *(l_u32x4a1*)X.at(p) = ldg16_src(X.dict + p);
+      for (int32_t p = (X.hs > X.lo ? X.hs : X.lo) + lane; p < X.pos; p += 64) *X.at(p) = X.out[p];
+    } else {
+      for (int32_t p = (X.hs > 0 ? X.hs : 0) + lane; p < X.pos; p += 64) *X.at(p) = X.out[p];
+    }
     k4_sync();
   }
   // repeat offsets in 32 bits: every offset a frame can use without an
@@ -3187,12 +3301,23 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
         // so the match bytes land at chunk offset ll - b; a chunk of literal
         // bytes only reads at slo)
         u32x4 fv0, fv1;
-        const bool far0 = far && slo >= 16;
+        bool far0 = far && slo >= 16;
+        // DICT: the lane's pieces (from slo - 15 on, the last one ending at
+        // shi; a piece of literal bytes only reads at slo, up to 16 bytes past
+        // shi: the dictionary buffer's padding) come from the dictionary or
+        // from the frame's output; a source that spans both goes to the
+        // frontier rounds (src16 merges the two there)
+        const uint8_t* fsrc = X.out;
+        if constexpr (DICT) {
+          const bool ind = shi <= X.lo;
+          far0 = far0 && (ind || slo - 16 >= X.lo);
+          fsrc = ind ? X.dict : (const uint8_t*)X.out;
+        }
         const uint32_t n0f = ll + ml;
         const uint32_t bb1 = n0f >= 32 ? 16u : (n0f > 16 ? n0f - 16 : 0u);
         if (far0) {
-          fv0 = ldg16_src(X.out + (uint32_t)(ll >= 16 ? slo : slo - (int32_t)ll));
-          if (n0f > 16) fv1 = ldg16_src(X.out + (uint32_t)(ll >= bb1 + 16 ? slo : slo + (int32_t)bb1 - (int32_t)ll));
+          fv0 = ldg16_src(fsrc + (uint32_t)(ll >= 16 ? slo : slo - (int32_t)ll));
+          if (n0f > 16) fv1 = ldg16_src(fsrc + (uint32_t)(ll >= bb1 + 16 ? slo : slo + (int32_t)bb1 - (int32_t)ll));
         }
 #else
         u32x4 fv0, fv1;
@@ -3282,7 +3407,7 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
             ZD_ISA_MARK("; ZDPUT>");
           };
           auto mload = [&](uint32_t bb) -> u32x4 {
-            return src_far ? ldg16_src(X.out + (uint32_t)msrc(bb)) : src_win ? lds16(X.at(msrc(bb))) : f4;
+            return src_far ? ldg16_src(fsrc + (uint32_t)msrc(bb)) : src_win ? lds16(X.at(msrc(bb))) : f4;
           };
           // chunks 0 and 1 (a far lane's match bytes were loaded above), then
           // four at a time, their loads first (no match here overlaps itself)
@@ -3436,7 +3561,7 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
            (unsigned long long)ph[7]);
 #endif
   if (lane == 0) {
-    S->out_len = (uint64_t)X.pos;
+    S->out_len = (uint64_t)(DICT ? X.pos - X.lo : X.pos);   // (a dictionary plan: the frame's own bytes)
     S->rep[0] = rep[0];
     S->rep[1] = rep[1];
     S->rep[2] = rep[2];
@@ -3463,6 +3588,30 @@ __global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute(const uint8_t* __
   const K4Lds M{(l_u8*)win + K4_WPAD, (l_u8*)pat, (l_u8*)stab, (l_u8*)stg, (l_u32*)codelut};
   k4_body<false>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x, f_end,
                  gridDim.x, redo, M, nullptr, nullptr);
+}
+
+// The streaming K4 of a dictionary plan (zd_plan_create_dict): every frame
+// starts at position F.out_len0 = the dictionary's content size, the
+// positions below it are `dict` (one buffer shared by all frames, 16 readable
+// bytes on both sides of the content), the frame's own bytes land at F.out as
+// without a dictionary.
+__global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute_dict(const uint8_t* __restrict__ src, uint8_t* outbase,
+                                                   const FrameDesc* __restrict__ frames, FrameState* fstate,
+                                                   const BlockRec* __restrict__ blocks,
+                                                   const CompBlock* __restrict__ comp,
+                                                   const CompState* __restrict__ cstate,
+                                                   const uint8_t* __restrict__ lits,
+                                                   const uint64_t* __restrict__ seqs,
+                                                   const uint16_t* __restrict__ fses, uint32_t f_begin,
+                                                   uint32_t f_end, const uint8_t* __restrict__ dict) {
+  __shared__ __attribute__((aligned(16))) uint8_t win[K4_WPAD + K4_C];
+  __shared__ __attribute__((aligned(16))) uint8_t pat[64];
+  __shared__ __attribute__((aligned(16))) uint8_t stab[3 * FSE_TAB];
+  __shared__ __attribute__((aligned(16))) uint8_t stg[K4_STG + 16];
+  __shared__ uint32_t codelut[2 * 64];
+  const K4Lds M{(l_u8*)win + K4_WPAD, (l_u8*)pat, (l_u8*)stab, (l_u8*)stg, (l_u32*)codelut};
+  k4_body<false, true>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x,
+                       f_end, gridDim.x, nullptr, M, nullptr, nullptr, dict);
 }
 
 // ---------------------------------------------------------------------------
@@ -5692,6 +5841,11 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     if (n && k4_work) {  // frames on the streaming K4 (K4F's, K4J's and K0's exit at once)
       const bool tm = !redo && k4_work;
       if (tm) if ((e = dom(DOM_K4, 0)) != hipSuccess) return e;
+      if (a.dict)                              // a dictionary plan (never fused: no redo pass)
+        hipLaunchKernelGGL(zd_k_execute_dict, dim3(n), dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp,
+                           (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
+                           (const uint16_t*)fses, f0, f1, a.dict);
+      else
       hipLaunchKernelGGL(zd_k_execute, dim3(n),
                          dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp, (const CompState*)cstate,
                          (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs, (const uint16_t*)fses, f0, f1, redo);
@@ -5797,14 +5951,17 @@ namespace zd {
 // from their device copies, block states, K1's tree list and deep-pool
 // counters, K4J's round counters and done flags (six copy / fill launches
 // before, ~5 us each on the path of a few-frame plan).
-__global__ __launch_bounds__(256) void zd_k_reset(uint8_t* ws, Workspace W, uint64_t fs_words, uint64_t cs_words,
-                                                  uint32_t jp_words, uint64_t jdone_bytes) {
+// cs_keep: the leading words of the block states that stay (a dictionary
+// plan's prebuilt comp 0, written once at plan creation; zd_k_reset_dict).
+__device__ __attribute__((always_inline)) inline void reset_body(uint8_t* ws, const Workspace& W, uint64_t fs_words,
+                                                                 uint64_t cs_words, uint32_t jp_words,
+                                                                 uint64_t jdone_bytes, uint32_t cs_keep) {
   const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x, nt = (uint64_t)gridDim.x * 256;
   uint32_t* fs = (uint32_t*)(ws + W.frame_state);
   const uint32_t* fs0 = (const uint32_t*)(ws + W.frame_state0);
   for (uint64_t i = t; i < fs_words; i += nt) fs[i] = fs0[i];
   uint32_t* cs = (uint32_t*)(ws + W.comp_state);
-  for (uint64_t i = t; i < cs_words; i += nt) cs[i] = 0;
+  for (uint64_t i = t + cs_keep; i < cs_words; i += nt) cs[i] = 0;
   if (t == 0) {
     *(uint32_t*)(ws + W.huge) = 0;
     *(uint32_t*)(ws + W.deep) = 0;
@@ -5816,15 +5973,33 @@ __global__ __launch_bounds__(256) void zd_k_reset(uint8_t* ws, Workspace W, uint
   for (uint64_t i = t; i < n16; i += nt) jd[i] = (u32x4){0, 0, 0, 0};
   if (t < jdone_bytes % 16) (ws + W.jdone)[16 * n16 + t] = 0;
 }
+__global__ __launch_bounds__(256) void zd_k_reset(uint8_t* ws, Workspace W, uint64_t fs_words, uint64_t cs_words,
+                                                  uint32_t jp_words, uint64_t jdone_bytes) {
+  reset_body(ws, W, fs_words, cs_words, jp_words, jdone_bytes, 0);
+}
+__global__ __launch_bounds__(256) void zd_k_reset_dict(uint8_t* ws, Workspace W, uint64_t fs_words, uint64_t cs_words,
+                                                       uint32_t jp_words, uint64_t jdone_bytes, uint32_t cs_keep) {
+  reset_body(ws, W, fs_words, cs_words, jp_words, jdone_bytes, cs_keep);
+}
 hipError_t launch_reset(uint8_t* ws, const Workspace& W, uint64_t n_frames, uint64_t n_comps, bool k4j,
-                        uint64_t j_pieces, hipStream_t s) {
+                        uint64_t j_pieces, hipStream_t s, uint32_t keep_comps) {
   const uint64_t fs_words = n_frames * sizeof(FrameState) / 4, cs_words = std::max<uint64_t>(n_comps, 1) * sizeof(CompState) / 4;
   const uint32_t jp_words = k4j ? (uint32_t)(J_MAX_ROUNDS + 1) : 0u;
   const uint64_t jdone = k4j ? std::max<uint64_t>(j_pieces, 1) : 0;
   const uint64_t work = std::max(std::max(fs_words, cs_words), jdone / 16 + 16);
   const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, (work + 1023) / 1024);
   static_assert(sizeof(FrameState) % 4 == 0 && sizeof(CompState) % 4 == 0, "zd_k_reset: u32 words");
-  hipLaunchKernelGGL(zd_k_reset, dim3(grid), dim3(256), 0, s, ws, W, fs_words, cs_words, jp_words, jdone);
+  if (keep_comps)
+    hipLaunchKernelGGL(zd_k_reset_dict, dim3(grid), dim3(256), 0, s, ws, W, fs_words, cs_words, jp_words, jdone,
+                       keep_comps * (uint32_t)(sizeof(CompState) / 4));
+  else
+    hipLaunchKernelGGL(zd_k_reset, dim3(grid), dim3(256), 0, s, ws, W, fs_words, cs_words, jp_words, jdone);
+  return hipGetLastError();
+}
+
+hipError_t launch_dict_tables(const uint8_t* d_dict, uint32_t n, uint16_t* d_lut, uint16_t* d_fse, DictTables* d_res,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(zd_k_dict_tables, dim3(1), dim3(64), 0, s, d_dict, n, d_lut, d_fse, d_res);
   return hipGetLastError();
 }
 

@@ -38,14 +38,32 @@ struct LaunchArgs {
   // fusion kept; bit g of *dom_used is set when group g launched
   hipEvent_t* dom_events = nullptr;
   uint32_t* dom_used = nullptr;
+  // a dictionary plan (zd_plan_create_dict): the dictionary's content on the
+  // device (frame positions [0, FrameDesc::out_len0)); the streaming K4 runs as
+  // zd_k_execute_dict
+  const uint8_t* dict = nullptr;
 };
 
 // K1 table parse/build -> K2 Huffman literals -> K3 FSE sequences -> K4 execute.
 hipError_t launch_pipeline(const LaunchArgs& a);
 
 // zd_decode_async's state reset (frame / block states, K1 and K4J counters, K4J done flags).
+// keep_comps: the leading block states left as they are (a dictionary plan's prebuilt comp)
 hipError_t launch_reset(uint8_t* ws, const Workspace& W, uint64_t n_frames, uint64_t n_comps, bool k4j,
-                        uint64_t j_pieces, hipStream_t s);
+                        uint64_t j_pieces, hipStream_t s, uint32_t keep_comps = 0);
+
+// zd_k_dict_tables' result (zd_dict_create reads it once)
+struct DictTables {
+  int32_t status;          // ZD_OK or the failing description's code
+  uint32_t rep_off;        // byte offset of the three repeat offsets in the dictionary
+  uint32_t huf_bits;       // maxBits of the Huffman tree
+  uint8_t al[3];           // accuracy logs, LL | OF | ML
+  uint8_t pad;
+};
+// The tables of a formatted dictionary d_dict[0, n) into a LUT slot (LUT_ENTRIES
+// u16) and an FSE slot (FSE_SLOT u16), as a prebuilt comp's.
+hipError_t launch_dict_tables(const uint8_t* d_dict, uint32_t n, uint16_t* d_lut, uint16_t* d_fse, DictTables* d_res,
+                              hipStream_t s);
 
 // Copies frame outputs from staging (at cap offsets) to exact offsets.
 hipError_t launch_compact(const uint8_t* staging, uint8_t* dst, const uint64_t* d_from,

@@ -67,6 +67,13 @@ struct PlanCtx {
   bool fused;              // zd_k_fused plan: no K4F, 128-byte aligned literal and record slots
   int k4j_mode;
   uint32_t k4j_min;        // compressed blocks a frame needs for K4J (automatic mode)
+  // A dictionary plan (zd_plan_create_dict): out_len0 is the dictionary's
+  // content size, positions before the frame that live in the dictionary's
+  // buffer, not in the output: a frame's region starts at its own first byte
+  // (K0's destinations, FrameState::out_len and the capacity count the
+  // frame's own bytes).  dict_id: the dictionary's ID (0: raw content).
+  bool dict;
+  uint32_t dict_id;
 };
 
 // Where the filling pass writes: the plan's host vectors (small plans, the
@@ -104,7 +111,14 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   int32_t tab_prev[3] = {X.prev_tab[0], X.prev_tab[1], X.prev_tab[2]};
   uint64_t bound = 0;
   bool seqs_in_frame = false;
-  const bool frame_failed_host = hf.key != KEY_NONE;
+  // a frame that names another dictionary stops the plan like a frame that
+  // failed to index (no block of it is planned to run)
+  if (X.dict && hf.d.kind == ZD_FRAME_ZSTD && hf.d.dict_id != UINT64_MAX && hf.d.dict_id != 0 &&
+      hf.d.dict_id != X.dict_id)
+    fs.key = plan_min(fs.key, make_key(PH_PARSE, 0, PS_STRUCT, 0, ZD_E_DICT_MISMATCH));
+  const bool frame_failed_host = fs.key != KEY_NONE;
+  // bytes of the frame's region before its first own byte (the context API's existing output)
+  const uint64_t own0 = X.dict ? 0 : X.out_len0;
   uint64_t jseg = 0;
   // a re-plan of a frame that overran (zd_plan_decompress): by identity, the
   // counting pass numbers each part's frames from 0
@@ -223,7 +237,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
                                      : ((X.k4j_auto && hf.ncomp >= X.k4j_min) || cap > K4_MAX_FRAME_OUT));
   // larger frames with sequences that K4J does not take (forced off, or past
   // its 32 GiB) are outside the GPU path's domain
-  if (!to_j && cap > K4_MAX_FRAME_OUT && seqs_in_frame)
+  if (!to_j && cap + (X.dict ? X.out_len0 : 0) > K4_MAX_FRAME_OUT && seqs_in_frame)
     fs.key = plan_min(fs.key, make_key(PH_LIMIT, 0, 0, 0, ZD_E_OUT_OF_DOMAIN));
   if (to_j) {
     fd.lds = 2;
@@ -276,12 +290,12 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
     for (; k < fd.nblocks; k++) {
       const HostBlock& hb = hblocks[hf.b0 + k];
       if (hb.type != 0 && hb.type != 1 && hb.type != 4) break;
-      if (X.out_len0 + pre + hb.size > cap) break;
+      if (own0 + pre + hb.size > cap) break;
       for (uint64_t x = 0; x < hb.size; x += COPY_PIECE) {
         if (FILL) {
           CopyDesc cd{};
           cd.src = hb.src + (hb.type == 1 ? 0 : x);
-          cd.dst = c.out + X.out_len0 + pre + x;
+          cd.dst = c.out + own0 + pre + x;
           cd.size = (uint32_t)plan_min<uint64_t>(COPY_PIECE, hb.size - x);
           cd.fill = hb.type == 1 ? (0x100u | hb.rle) : 0u;
           S.copies[c.copies] = cd;
@@ -296,7 +310,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
     // executor runs it (a launch less when no frame needs the streaming K4)
     if (k == fd.nblocks && fs.key == KEY_NONE) {
       fd.lds = 3;
-      fs.out_len = X.out_len0 + pre;
+      fs.out_len = own0 + pre;
       c.k0only++;
     }
   }

@@ -68,7 +68,12 @@ ZD_HD inline void zero_bytes(void* p, size_t n) {
 // Literals section header + the walk-visible parts of the section
 // (literals.rs:88-206) and of the sequences header (sequences.rs:52-87 and
 // the mode byte of 91-143).  The block content is base[off, off + size).
-ZD_HD inline int parse_compressed(const uint8_t* base, uint64_t off, uint32_t size, CompBlock* cb, WalkErr* e) {
+// rfc_empty_lits (dictionary plans, zd_plan_create_dict): a Raw literals
+// section of 0 bytes is accepted as RFC 8878 has it -- a record found wholly in
+// the dictionary has no literals -- where the reference's zero-length slice is
+// an EmptySliceError (parsing.rs, kept everywhere else).
+ZD_HD inline int parse_compressed(const uint8_t* base, uint64_t off, uint32_t size, CompBlock* cb, WalkErr* e,
+                                  bool rfc_empty_lits = false) {
   Bytes np{base + off, size};
   const uint8_t* start = np.p;
   auto rel = [&]() { return (uint32_t)(np.p - start); };
@@ -103,7 +108,8 @@ ZD_HD inline int parse_compressed(const uint8_t* base, uint64_t off, uint32_t si
   if (lt == LIT_RAW) {
     const uint8_t* s;
     cb->lit_data = rel();
-    if (int r = np.slice(regen, &s)) return e->code = r;
+    if (regen || !rfc_empty_lits)
+      if (int r = np.slice(regen, &s)) return e->code = r;
   } else if (lt == LIT_RLE) {
     if (int r = np.u8(&cb->lit_rle)) return e->code = r;
   } else {
@@ -215,7 +221,7 @@ ZD_HD inline int parse_header(Bytes& in, zd_frame_desc* f) {
 // so far; S.push(block)).  On error, hf->key/status hold the failure; the
 // blocks parsed before (and the failing one, with its host_stage) are kept.
 template <typename SINK>
-ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK& S) {
+ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK& S, bool rfc_empty_lits = false) {
   zd_frame_desc& f = hf->d;
   zero_bytes(&f, sizeof f);
   f.src_offset = (uint64_t)(in.p - base);
@@ -273,7 +279,7 @@ ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK
         cb.block_in_frame = bi;
         cb.host_stage = PS_ALL;
         WalkErr e;
-        int r = parse_compressed(base, hb.src, hb.size, &cb, &e);
+        int r = parse_compressed(base, hb.src, hb.size, &cb, &e, rfc_empty_lits);
         if (r) {
           cb.host_stage = (uint8_t)e.stage;
           push(hb);

@@ -15,7 +15,7 @@ from .parsing import ForwardByteParser
 from .frame import Frame, FrameIterator, Header, Skippable, ZStandard, MAX_WIN_SIZE
 from .block import Block
 from .decoding_context import DecodingContext
-from .batch import Plan, decompress, frames_index
+from .batch import Dictionary, Plan, decompress, frames_index
 
 __all__ = ["ZdError", "ForwardByteParser", "Frame", "FrameIterator", "Header", "Skippable", "ZStandard",
-           "MAX_WIN_SIZE", "Block", "DecodingContext", "Plan", "decompress", "frames_index"]
+           "MAX_WIN_SIZE", "Block", "DecodingContext", "Dictionary", "Plan", "decompress", "frames_index"]

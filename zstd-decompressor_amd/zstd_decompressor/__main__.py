@@ -1,6 +1,6 @@
 """Command line, mirroring the reference CLI (src/main.rs:7-60):
 
-    python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable]
+    python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]
 
 Decodes every frame of FILE on the GPU (the HIP pipeline behind zd_decompress)
 and writes the concatenated output to stdout or --output.  As in the
@@ -10,7 +10,9 @@ be UTF-8 (the reference's `String::from_utf8(res).unwrap()` panics otherwise:
 exit status 101).  --info prints one line per frame instead (the reference
 prints the parsed frames with `{:#x?}`).  Extra, beyond the reference:
 --check-checksums verifies Content_Checksum (XXH64) on the GPU and reports
-mismatches on stderr (the reference computes and never enforces it).
+mismatches on stderr (the reference computes and never enforces it);
+-D DICT decodes every frame with the dictionary file DICT (formatted or raw
+content), as zstd's own -D does.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import argparse
 import sys
 
 from . import _lib
-from .batch import Plan, frames_index
+from .batch import Dictionary, Plan, frames_index
 
 
 def _info(data: bytes) -> int:
@@ -50,12 +52,19 @@ def main(argv=None) -> int:
     ap.add_argument("-p", "--print-skippable", action="store_true", help="Output Skippable frames as well")
     ap.add_argument("--check-checksums", action="store_true",
                     help="verify Content_Checksum (XXH64) on the GPU; mismatches go to stderr (not in the reference)")
+    ap.add_argument("-D", dest="dictionary", metavar="dict",
+                    help="decode with this dictionary file, as zstd -D (not in the reference)")
     a = ap.parse_args(argv)
     data = open(a.filename, "rb").read()
     if a.info:
         return _info(data)
     import torch
-    plan = Plan(data, a.print_skippable)
+    try:
+        dictionary = Dictionary(open(a.dictionary, "rb").read()) if a.dictionary else None
+    except _lib.ZdError as e:
+        print(f"Error: dictionary: {e.name}", file=sys.stderr)
+        return 1
+    plan = Plan(data, a.print_skippable, dictionary=dictionary)
     dev = torch.device("cuda", torch.cuda.current_device())
     d_src = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
     if data:

@@ -78,6 +78,12 @@ SIGNATURES = {
     "zd_plan_kernel_times": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]),
     "zd_decompress": (C.c_int, [_vp, _sz, _vp, _sz, _szp, C.c_uint32]),
     "zd_plan_decompress": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _szp]),
+    "zd_dict_create": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
+    "zd_dict_destroy": (None, [_vp]),
+    "zd_dict_info": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                               C.POINTER(C.c_int)]),
+    "zd_plan_create_dict": (C.c_int, [_vp, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "zd_decompress_dict": (C.c_int, [_vp, _sz, _vp, _sz, _szp, C.c_uint32, _vp]),
     "zd_context_new": (C.c_int, [C.c_uint64, C.POINTER(_vp)]),
     "zd_context_free": (None, [_vp]),
     "zd_block_decode": (C.c_int, [_vp, _vp, _sz, _szp, C.POINTER(C.c_int)]),
@@ -202,6 +208,7 @@ CTX_WINDOW_SIZE_TOO_BIG, NULL_OFFSET, IMPOSSIBLE_VALUE = -40, -41, -42
 RESERVED_BLOCK_TYPE = -50
 UNRECOGNIZED_MAGIC, FRAME_RESERVED_SET, MISSING_CHECKSUM, WINDOW_SIZE_TOO_BIG = -60, -61, -64, -66
 REF_PANIC, OUT_OF_DOMAIN, DST_TOO_SMALL, INVALID_ARG, HIP, NO_MEMORY, NOT_DECODED = -90, -91, -92, -93, -94, -95, -96
+DICT_CORRUPTED, DICT_MISMATCH = -98, -99
 F_SKIPPABLE = 1
 F_BLOCK_PARALLEL = 2   # every frame with a compressed block -> K4J (block-parallel execute)
 F_FRAME_SERIAL = 4     # no frame -> K4J

@@ -46,20 +46,52 @@ def run_plan(plan, p, n):
     return st, _lib.take(out, min(ol.value, cap))
 
 
-def _decompress(data: bytes, flags: int):
+class Dictionary:
+    """zd_dict: a zstd dictionary (RFC 8878 5) on the current device, formatted
+    (magic 0xEC30A437: ID, entropy tables, repeat offsets, content) or raw
+    content (any other bytes).  Pass it to Plan / decompress /
+    decompress_status as `dictionary=`; plans made with it keep it alive, so
+    close() before they are closed is fine."""
+
+    def __init__(self, data: bytes):
+        L = _lib.lib()
+        p, n, keep = _lib.buf(data)
+        h = C.c_void_p()
+        _lib.check(L.zd_dict_create(p, n, C.byref(h)), "zd_dict_create")
+        self._h = h
+        did, size, raw = C.c_uint32(), C.c_uint64(), C.c_int()
+        rep = (C.c_uint64 * 3)()
+        _lib.check(L.zd_dict_info(h, C.byref(did), C.byref(size), rep, C.byref(raw)), "zd_dict_info")
+        self.dict_id, self.content_size = did.value, size.value
+        self.repeat_offsets, self.raw_content = tuple(rep), bool(raw.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().zd_dict_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _decompress(data: bytes, flags: int, dictionary=None):
     """One plan (the host walk once) and zd_plan_decompress — what
     zd_decompress does, with the plan's output size read first."""
     p, n, keep = _lib.buf(data)
-    plan = Plan(data, bool(flags & _lib.F_SKIPPABLE), flags & ~_lib.F_SKIPPABLE)
+    plan = Plan(data, bool(flags & _lib.F_SKIPPABLE), flags & ~_lib.F_SKIPPABLE, dictionary=dictionary)
     try:
         return run_plan(plan, p, n)
     finally:
         plan.close()
 
 
-def decompress(data: bytes, print_skippable: bool = False) -> bytes:
-    """Decode every frame of `data` on the GPU (host in, host out)."""
-    st, out = _decompress(data, _lib.F_SKIPPABLE if print_skippable else 0)
+def decompress(data: bytes, print_skippable: bool = False, dictionary=None) -> bytes:
+    """Decode every frame of `data` on the GPU (host in, host out);
+    dictionary: a Dictionary every frame decodes with."""
+    st, out = _decompress(data, _lib.F_SKIPPABLE if print_skippable else 0, dictionary)
     _lib.check(st, "zd_decompress")
     return out
 
@@ -82,22 +114,28 @@ def decode_keyed(data: bytes, flags: int = 0):
         plan.close()
 
 
-def decompress_status(data: bytes, print_skippable: bool = False, flags: int = 0):
+def decompress_status(data: bytes, print_skippable: bool = False, flags: int = 0, dictionary=None):
     """(status, output of the frames before the first failure).  flags: extra
-    zd_plan flags (_lib.F_BLOCK_PARALLEL / F_FRAME_SERIAL pick the executor)."""
-    return _decompress(data, (_lib.F_SKIPPABLE if print_skippable else 0) | flags)
+    zd_plan flags (_lib.F_BLOCK_PARALLEL / F_FRAME_SERIAL pick the executor);
+    dictionary: a Dictionary every frame decodes with."""
+    return _decompress(data, (_lib.F_SKIPPABLE if print_skippable else 0) | flags, dictionary)
 
 
 class Plan:
     """zd_plan: host index + device workspace for one byte range of frames."""
 
-    def __init__(self, data: bytes, print_skippable: bool = False, flags: int = 0):
+    def __init__(self, data: bytes, print_skippable: bool = False, flags: int = 0, dictionary=None):
         L = _lib.lib()
         self._data = data
         p, n, self._keep = _lib.buf(data)
         h = C.c_void_p()
-        _lib.check(L.zd_plan_create(p, n, (_lib.F_SKIPPABLE if print_skippable else 0) | flags, C.byref(h)),
-                   "zd_plan_create")
+        f = (_lib.F_SKIPPABLE if print_skippable else 0) | flags
+        if dictionary is None:
+            _lib.check(L.zd_plan_create(p, n, f, C.byref(h)), "zd_plan_create")
+        else:
+            if not getattr(dictionary, "_h", None):
+                raise ValueError("the Dictionary is closed")
+            _lib.check(L.zd_plan_create_dict(p, n, f, dictionary._h, C.byref(h)), "zd_plan_create_dict")
         self._h = h
         self.info = PlanInfo()
         _lib.check(L.zd_plan_info_get(h, C.byref(self.info)), "zd_plan_info_get")
