@@ -386,6 +386,85 @@ int  zd_decompress_dict(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, 
                         uint32_t flags, const zd_dict* dict);
 
 /* ------------------------------------------------------------------ */
+/* Batches of scattered chunks (beyond the reference, whose input is    */
+/* one byte range of frames): N independently compressed chunks at N    */
+/* device addresses, each decoded into its own device buffer with its   */
+/* own status.                                                          */
+/* ------------------------------------------------------------------ */
+typedef struct zd_batch zd_batch;
+
+typedef struct zd_batch_info {
+  uint64_t nchunks;
+  uint64_t gathered_bytes;  /* the batch's own copy of the chunks (16-byte aligned, padded tails) */
+  uint64_t nblocks;
+  uint64_t nsequences;
+  uint64_t workspace_bytes; /* device memory the batch owns besides that copy */
+  uint32_t executors;       /* ZD_EXEC_* bits, as zd_plan_info.executors */
+  uint32_t reserved;
+  uint64_t gather_ns;       /* zd_batch_create: pointer-list upload + zd_k_gather */
+  uint64_t walk_ns;         /*   zd_k_walk_chunks (count, fill) + the index's way back */
+  uint64_t host_ns;         /*   descriptors (host work) */
+  uint64_t upload_ns;       /*   workspace allocation + descriptor upload */
+} zd_batch_info;
+
+/* A batch over nchunks chunks: chunk i is the src_bytes[i] bytes at device
+ * address d_src[i] and decodes into [d_dst[i], d_dst[i] + dst_cap[i]).  The
+ * four arrays are host arrays of nchunks entries.  A chunk holds exactly one
+ * zstd frame, with any number of skippable frames (skipped, never output)
+ * before and after it; a chunk of zero bytes or of skippable frames only is
+ * ZD_OK with length 0.  Chunks are independent: every chunk gets its own
+ * status, no chunk's failure touches another (ZD_E_NOT_DECODED never appears)
+ * and a failing chunk's length is 0:
+ *   the walk's own code        the chunk is not consumed entirely that way
+ *                              (ZD_E_UNRECOGNIZED_MAGIC, ZD_E_NOT_ENOUGH_BYTES,
+ *                              ...: trailing bytes, a truncated frame)
+ *   ZD_E_OUT_OF_DOMAIN         a second zstd frame in the chunk
+ *   ZD_E_DST_TOO_SMALL         a Frame_Content_Size above dst_cap[i] (found here:
+ *                              nothing of the chunk runs), or a frame that
+ *                              reaches dst_cap[i] while decoding
+ *   anything else              what a plan gives the same frame
+ * A frame's capacity is the smaller of dst_cap[i] and what a plan reserves
+ * (its Frame_Content_Size when usable, else 128 KiB per block); a frame
+ * without a Frame_Content_Size decodes in place in its own buffer.  No byte
+ * outside [d_dst[i], d_dst[i] + dst_cap[i]) is written.
+ * The call copies the chunks into one buffer the batch owns (zd_k_gather:
+ * exactly the bytes [d_src[i], d_src[i] + src_bytes[i]) are read, at any
+ * alignment, so the caller owes no ZD_SRC_PADDING and may release the sources
+ * when the call returns), walks the chunks' headers on the GPU
+ * (zd_k_walk_chunks, one lane per chunk) and builds the descriptors on the
+ * host.  Synchronises `stream`.
+ * flags: the executor and chain flags of a plan, with a plan's routing;
+ * ZD_F_SKIPPABLE is ZD_E_INVALID_ARG.  dict (may be NULL): every chunk decodes
+ * with it, under zd_plan_create_dict's limits (the streaming executor only).
+ * ZD_E_INVALID_ARG, before any HIP call: a NULL array with nchunks > 0, a NULL
+ * d_src[i] with src_bytes[i] > 0, a NULL d_dst[i] with dst_cap[i] > 0,
+ * destination ranges that overlap. */
+int  zd_batch_create(const void* const* d_src, const uint64_t* src_bytes,
+                     void* const* d_dst, const uint64_t* dst_cap, size_t nchunks,
+                     uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out);
+int  zd_batch_info_get(const zd_batch* batch, zd_batch_info* info);
+/* Launches the decode of every chunk on `stream`, ending with a kernel that
+ * writes the batch's device result arrays (zd_batch_device_results).  No
+ * allocation, no host synchronisation, like zd_decode_async; may be called
+ * again (the destinations are decoded again). */
+int  zd_batch_decode_async(zd_batch* batch, void* stream);
+/* The device result arrays, owned by the batch (nchunks entries each): after
+ * the work zd_batch_decode_async queued, d_status[i] is chunk i's status and
+ * d_len[i] its decoded length (0 unless ZD_OK).  Work queued behind it on the
+ * same stream reads them without a host round trip. */
+int  zd_batch_device_results(const zd_batch* batch, const int32_t** d_status, const uint64_t** d_len);
+/* Waits for `stream` and returns the same arrays (host arrays of cap >=
+ * nchunks entries, either may be NULL) and the number of chunks that are not
+ * ZD_OK.  A chunk whose block-parallel execution did not converge (K4J's
+ * rounds, the case zd_plan_decompress plans again) is decoded again here on
+ * the streaming executor, and the device arrays are updated. */
+int  zd_batch_results(zd_batch* batch, void* stream, int32_t* status, uint64_t* len, size_t cap, uint64_t* nfailed);
+/* zd_plan_checksums per chunk, after zd_batch_results: ok[i] = 1 / 0 / -1
+ * (matches / differs / no Content_Checksum or not decoded), hash[i] = XXH64. */
+int  zd_batch_checksums(zd_batch* batch, void* stream, int32_t* ok, uint64_t* hash);
+void zd_batch_destroy(zd_batch* batch);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU: frame-range sharding + RCCL gather.      */
 /* Frames are independent (a fresh DecodingContext each, frame.rs:     */
 /* 232-237) and the CLI concatenates their outputs, stopping at the    */

@@ -108,6 +108,7 @@ struct zd_plan {
   bool fused = false;                           // zd_k_fused plan (build_plan fuse_plan)
   bool last_fused = false;                      // the last zd_decode_async launched zd_k_fused
   std::vector<uint64_t> frame_out, frame_cap;   // output offset and capacity per frame
+  std::vector<uint64_t> place_out, place_cap;   // a batch's per-frame placement (PlanCtx::place_out), else empty
   bool staged = false;
   std::unique_lock<std::mutex> stage_lock;      // the pinned staging, from build_plan to upload_plan
   zd_plan_info info{};
@@ -403,6 +404,8 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   X.flags = P->flags;
   X.dict = P->dict != nullptr;
   X.dict_id = P->dict ? P->dict->id : 0;
+  X.place_out = P->place_out.empty() ? nullptr : P->place_out.data();
+  X.place_cap = P->place_out.empty() ? nullptr : P->place_cap.data();
   RouteIn in{};
   in.cus = (uint32_t)(k3_slots() / 64);
   in.nframes = P->nframes;
@@ -537,7 +540,11 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
   run_parts(np, [&](size_t k) {
     const HostPart& hp = P->parts[k];
     PlanCounts c;
+    // (a batch's placement is by plan frame index: the part counts from its
+    // first frame's, taken off again below)
+    if (X.place_out) c.frames = P->part_f0[k];
     for (const HostFrame& hf : hp.frames) plan_frame<false, JMax>(X, hf, hp.blocks.data(), c, none, nullptr);
+    if (X.place_out) c.frames -= P->part_f0[k];
     if (X.fused) {          // parts start aligned, so the filling pass pads exactly as this count did
       c.lits = align_up(c.lits, 128);
       c.nrec = align_up(c.nrec, 16);
@@ -719,7 +726,8 @@ int upload_staging(zd_plan* P) {
   return 0;
 }
 
-int upload_plan(zd_plan* P) {
+// the workspace and the descriptors at its head
+int upload_desc(zd_plan* P) {
   HIPCHK(hipGetDevice(&P->dev));
   HIPCHK(ws_alloc(P->dev, P->W.total, &P->d_ws, &P->ws_bytes));
   if (P->staged) {
@@ -747,7 +755,30 @@ int upload_plan(zd_plan* P) {
     for (const Piece& q : pieces)
       if (q.bytes) HIPCHK(hipMemcpy(P->d_ws + q.off, q.p, q.bytes, hipMemcpyHostToDevice));
   }
+  return 0;
+}
+
+int upload_plan(zd_plan* P) {
+  if (int r = upload_desc(P)) return r;
   return upload_staging(P);
+}
+
+// A formatted dictionary's prebuilt comp 0, once per plan: its slots and its
+// state (zd_k_reset leaves comp 0's state alone, launch_reset keep_comps; no
+// launch writes the slots)
+int upload_dict_tables(zd_plan* P) {
+  const DictData* dict = P->dict.get();
+  if (!dict || dict->raw) return 0;
+  CompState pcs{};
+  pcs.huf_bits = dict->huf_bits;
+  for (int k = 0; k < 3; k++) pcs.al[k] = dict->al[k];
+  if (hipMemcpy(P->d_ws + P->W.luts, dict->d_lut, LUT_ENTRIES * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
+      hipMemcpy(P->d_ws + P->W.fses, dict->d_fse, FSE_SLOT * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
+      hipMemcpy(P->d_ws + P->W.comp_state, &pcs, sizeof pcs, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    return ZD_E_HIP;
+  }
+  return 0;
 }
 
 // A plan's second stream and its fork/join events, kept for the next plans
@@ -1559,19 +1590,7 @@ static int plan_create(const uint8_t* src, const uint8_t* d_src, size_t n, uint3
             std::chrono::duration<double, std::milli>(ti - t0).count(),
             std::chrono::duration<double, std::milli>(t1 - ti).count());
   int r = P->dev_built ? upload_staging(P) : upload_plan(P);
-  if (!r && dict && !dict->raw) {
-    // the prebuilt comp's slots and state, once: zd_k_reset leaves comp 0's
-    // state alone (launch_reset keep_comps), no launch writes the slots
-    CompState pcs{};
-    pcs.huf_bits = dict->huf_bits;
-    for (int k = 0; k < 3; k++) pcs.al[k] = dict->al[k];
-    if (hipMemcpy(P->d_ws + P->W.luts, dict->d_lut, LUT_ENTRIES * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
-        hipMemcpy(P->d_ws + P->W.fses, dict->d_fse, FSE_SLOT * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
-        hipMemcpy(P->d_ws + P->W.comp_state, &pcs, sizeof pcs, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipGetLastError();
-      r = ZD_E_HIP;
-    }
-  }
+  if (!r) r = upload_dict_tables(P);
   const auto tu = std::chrono::steady_clock::now();
   // the second stream and its events (K2 beside K3) exist
   // from here on, so zd_decode_async creates nothing
@@ -1679,12 +1698,10 @@ int zd_plan_kernel_times(zd_plan* P, const char** names, float* ms, int cap, int
   return ZD_OK;
 }
 
-int zd_decode_async(zd_plan* P, const uint8_t* d_src, uint8_t* d_dst, size_t dst_cap, void* stream) {
-  if (!P) return ZD_E_INVALID_ARG;
-  // out_bytes bounds the output in both layouts (the staging layout is
-  // compacted into d_dst by zd_plan_results)
-  if (dst_cap < P->info.out_bytes) return ZD_E_DST_TOO_SMALL;
-  hipStream_t s = (hipStream_t)stream;
+// The launch of zd_decode_async: the pipeline over the plan's descriptors,
+// frame f's output at out + FrameDesc::out (zd_decode_async: d_dst or the
+// plan's staging; a batch: the lowest destination, zd_batch_decode_async).
+static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStream_t s) {
   // frame and block states are reset every launch (keys, lengths, repeat
   // offsets, flags) from device-resident copies: no host memory is read, so
   // a graph captured around this call replays the reset
@@ -1708,7 +1725,7 @@ int zd_decode_async(zd_plan* P, const uint8_t* d_src, uint8_t* d_dst, size_t dst
   LaunchArgs a{};
   a.src = d_src;
   a.src_size = P->info.src_bytes;
-  a.out = P->info.out_exact ? d_dst : P->d_staging;
+  a.out = out;
   a.ws = P->d_ws;
   a.W = P->W;
   a.n_tables = (uint32_t)P->n_tables;
@@ -1779,6 +1796,14 @@ int zd_decode_async(zd_plan* P, const uint8_t* d_src, uint8_t* d_dst, size_t dst
   P->launched = true;
   P->last_stream = s;
   return ZD_OK;
+}
+
+int zd_decode_async(zd_plan* P, const uint8_t* d_src, uint8_t* d_dst, size_t dst_cap, void* stream) {
+  if (!P) return ZD_E_INVALID_ARG;
+  // out_bytes bounds the output in both layouts (the staging layout is
+  // compacted into d_dst by zd_plan_results)
+  if (dst_cap < P->info.out_bytes) return ZD_E_DST_TOO_SMALL;
+  return decode_launch(P, d_src, P->info.out_exact ? d_dst : P->d_staging, (hipStream_t)stream);
 }
 
 int zd_plan_results(zd_plan* P, uint8_t* d_dst, void* stream, int32_t* frame_status, uint64_t* frame_len,
@@ -2175,6 +2200,355 @@ int zd_decompress_dict(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, s
   r = zd_plan_decompress(P, src, n, dst, cap, out_len);
   zd_plan_destroy(P);
   return r;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Batches of scattered chunks (zd_batch_create): the chunks, copied into one
+// buffer the batch owns, are the frames of one plan over that buffer -- chunk
+// i is frame i -- whose frames are placed at the chunks' own destinations
+// (PlanCtx::place_out) and never stop one another.
+// ===========================================================================
+struct zd_batch {
+  zd_plan* P = nullptr;                  // null: a batch of no chunks
+  size_t n = 0;
+  uint32_t flags = 0;
+  std::shared_ptr<DictData> dict;
+  int dev = -1;
+  uint8_t* d_gather = nullptr;           // the chunks' copies, 16-byte aligned, zero bytes between them
+  uint64_t gather_alloc = 0;
+  uint8_t* outbase = nullptr;            // the lowest destination
+  uint8_t* d_arr = nullptr;              // one allocation for the arrays below
+  uint64_t arr_bytes = 0;
+  uint64_t *d_src = nullptr, *d_size = nullptr, *d_off = nullptr, *d_out = nullptr;   // ChunkList, output offsets
+  GatherPiece* d_pieces = nullptr;
+  uint64_t *d_boff = nullptr, *d_len = nullptr, *d_hash = nullptr;
+  int32_t* d_status = nullptr;
+  uint32_t* d_nblk = nullptr;
+  uint8_t* d_bind = nullptr;
+  std::vector<uint64_t> goff, src_size, dst, dst_cap;
+  std::vector<int32_t> h_status;         // the last zd_batch_results
+  std::vector<uint64_t> h_len;
+  bool have_results = false;
+  bool launched = false;
+  zd_batch_info info{};
+};
+
+extern "C" {
+
+void zd_batch_destroy(zd_batch* B) {
+  if (!B) return;
+  if (B->P) zd_plan_destroy(B->P);        // (waits for the work the batch launched)
+  ws_release(B->d_gather, B->gather_alloc, B->dev);
+  if (B->d_arr) (void)hipFree(B->d_arr);
+  delete B;
+}
+
+int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst, const uint64_t* dst_cap,
+                    size_t nchunks, uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out) {
+  // ---- argument checks: no HIP call before they are done ----
+  if (!out || (flags & ZD_F_SKIPPABLE)) return ZD_E_INVALID_ARG;
+  if (nchunks && (!d_src || !src_bytes || !d_dst || !dst_cap)) return ZD_E_INVALID_ARG;
+  if (nchunks >= (1ull << 31) || (dict && !dict->p)) return ZD_E_INVALID_ARG;
+  const size_t n = nchunks;
+  {
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;      // destinations of at least one byte
+    for (size_t i = 0; i < n; i++) {
+      if ((!d_src[i] && src_bytes[i]) || (!d_dst[i] && dst_cap[i])) return ZD_E_INVALID_ARG;
+      const uint64_t a = (uint64_t)(uintptr_t)d_dst[i];
+      if (a + dst_cap[i] < a || (uint64_t)(uintptr_t)d_src[i] + src_bytes[i] < (uint64_t)(uintptr_t)d_src[i])
+        return ZD_E_INVALID_ARG;
+      if (dst_cap[i]) ranges.push_back({a, dst_cap[i]});
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t k = 1; k < ranges.size(); k++)
+      if (ranges[k].first < ranges[k - 1].first + ranges[k - 1].second) return ZD_E_INVALID_ARG;
+  }
+  zd_batch* B = new (std::nothrow) zd_batch();
+  if (!B) return ZD_E_NO_MEMORY;
+  struct Drop { void operator()(zd_batch* b) const { zd_batch_destroy(b); } };
+  std::unique_ptr<zd_batch, Drop> hold(B);
+  B->n = n;
+  B->flags = flags;
+  B->info.nchunks = n;
+  if (!n) { *out = hold.release(); return ZD_OK; }
+
+  HIPCHK(hipGetDevice(&B->dev));
+  if (dict) {
+    if (dict->p->dev != B->dev) return ZD_E_INVALID_ARG;
+    B->dict = dict->p;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  // ---- the gathered layout and zd_k_gather's pieces ----
+  B->goff.resize(n);
+  B->src_size.assign(src_bytes, src_bytes + n);
+  B->dst.resize(n);
+  B->dst_cap.assign(dst_cap, dst_cap + n);
+  uint64_t total = 0, npieces = 0;
+  uint64_t lowest = UINT64_MAX;
+  for (size_t i = 0; i < n; i++) {
+    B->goff[i] = total;
+    total += align_up(src_bytes[i], 16) + ZD_SRC_PADDING;
+    npieces += std::max<uint64_t>(1, (src_bytes[i] + COPY_PIECE - 1) / COPY_PIECE);
+    B->dst[i] = (uint64_t)(uintptr_t)d_dst[i];
+    if (d_dst[i]) lowest = std::min(lowest, B->dst[i]);
+  }
+  if (lowest == UINT64_MAX) lowest = 0;
+  if (npieces * (COPY_PIECE / 4096) >= (1ull << 31)) return ZD_E_OUT_OF_DOMAIN;   // zd_k_gather's grid
+  B->outbase = (uint8_t*)(uintptr_t)lowest;
+  // the uploaded head of d_arr: src | size | off | out | pieces; then the device-written arrays
+  const uint64_t head_words = 4 * n + npieces;
+  std::vector<uint64_t> head(head_words);
+  for (size_t i = 0; i < n; i++) {
+    head[i] = (uint64_t)(uintptr_t)d_src[i];
+    head[n + i] = src_bytes[i];
+    head[2 * n + i] = B->goff[i];
+    head[3 * n + i] = d_dst[i] ? B->dst[i] - lowest : 0;
+  }
+  {
+    GatherPiece* gp = (GatherPiece*)(head.data() + 4 * n);
+    static_assert(sizeof(GatherPiece) == 8, "GatherPiece: one u64 slot");
+    uint64_t k = 0;
+    for (size_t i = 0; i < n; i++) {
+      const uint64_t np = std::max<uint64_t>(1, (src_bytes[i] + COPY_PIECE - 1) / COPY_PIECE);
+      if (np >= (1ull << 32)) return ZD_E_OUT_OF_DOMAIN;
+      for (uint64_t q = 0; q < np; q++) gp[k++] = GatherPiece{(uint32_t)i, (uint32_t)q};
+    }
+  }
+  B->arr_bytes = 8 * (head_words + 3 * n) + 4 * n + 4 * n + align_up(n, 8);
+  HIPCHK(hipMalloc(&B->d_arr, B->arr_bytes));
+  {
+    uint64_t* a = (uint64_t*)B->d_arr;
+    B->d_src = a; B->d_size = a + n; B->d_off = a + 2 * n; B->d_out = a + 3 * n;
+    B->d_pieces = (GatherPiece*)(a + 4 * n);
+    B->d_boff = a + head_words; B->d_len = B->d_boff + n; B->d_hash = B->d_len + n;
+    B->d_status = (int32_t*)(B->d_hash + n);
+    B->d_nblk = (uint32_t*)(B->d_status + n);
+    B->d_bind = (uint8_t*)(B->d_nblk + n);
+  }
+  HIPCHK(ws_alloc(B->dev, std::max<uint64_t>(total, 16), &B->d_gather, &B->gather_alloc));
+  HIPCHK(hipMemcpyAsync(B->d_arr, head.data(), 8 * head_words, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(B->d_boff, 0, B->arr_bytes - 8 * head_words, s));
+  const ChunkList L{B->d_src, B->d_size, B->d_off};
+  HIPCHK(launch_gather(L, B->d_gather, B->d_pieces, npieces, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const auto t1 = std::chrono::steady_clock::now();
+
+  // ---- zd_k_walk_chunks: count, the blocks' places, fill; the index comes back ----
+  zd_plan* P = new (std::nothrow) zd_plan();
+  if (!P) return ZD_E_NO_MEMORY;
+  B->P = P;
+  P->flags = flags;
+  P->dict = B->dict;
+  const bool rfc_empty_lits = P->dict != nullptr;
+  std::vector<uint8_t> bind(n, 0);
+  P->place_out.assign(head.begin() + 3 * (long)n, head.begin() + 4 * (long)n);
+  P->place_cap = B->dst_cap;
+  {
+    DevWalkBufs& WB = dev_walk_bufs();
+    std::lock_guard<std::mutex> lk(WB.m);
+    if (WB.dev != B->dev) {                  // buffers of another device: start over
+      if (WB.d_wr) (void)hipFree(WB.d_wr);
+      if (WB.d_out) (void)hipFree(WB.d_out);
+      WB.d_wr = nullptr; WB.cap_wr = 0; WB.d_out = nullptr; WB.cap_out = 0;
+      WB.dev = B->dev;
+    }
+    HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, nullptr, nullptr, nullptr, false,
+                              s));
+    std::vector<uint32_t> nblk(n);
+    HIPCHK(hipMemcpyAsync(nblk.data(), B->d_nblk, 4 * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<uint64_t> boff(n);
+    uint64_t NB = 0;
+    for (size_t i = 0; i < n; i++) { boff[i] = NB; NB += nblk[i]; }
+    if (NB >= (1ull << 32)) return ZD_E_OUT_OF_DOMAIN;
+    const size_t fb = align_up(n * sizeof(HostFrame), 256), bytes = fb + NB * sizeof(HostBlock);
+    if (!grow_dev(WB.d_out, WB.cap_out, bytes) || !grow_pinned(WB.h_out, WB.cap_h, bytes)) return ZD_E_HIP;
+    WB.fb = fb;
+    WB.bytes = bytes;
+    HIPCHK(hipMemcpyAsync(B->d_boff, boff.data(), 8 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, B->d_boff, (HostFrame*)WB.d_out,
+                              (HostBlock*)(WB.d_out + fb), true, s));
+    const HostFrame* cfr = nullptr;
+    const HostBlock* bl = nullptr;
+    if (int r = dev_walk_download(WB, s, &cfr, &bl)) return r;
+    // a usable Frame_Content_Size above the chunk's capacity: found here, and
+    // nothing of the chunk runs; bind: the caller's capacity is below what the
+    // plan reserves for a frame without a usable one
+    HostFrame* fr = (HostFrame*)WB.h_out;
+    std::vector<const HostFrame*> kept(n);
+    for (size_t i = 0; i < n; i++) {
+      HostFrame& hf = fr[i];
+      kept[i] = &hf;
+      if (hf.d.kind != ZD_FRAME_ZSTD || hf.key != KEY_NONE) continue;
+      uint64_t bound = 0;
+      for (uint32_t k = 0; k < hf.nb; k++) bound += bl[hf.b0 + k].type == 2 ? MAX_BLOCK_OUT : bl[hf.b0 + k].size;
+      const bool usable = hf.d.content_size != UINT64_MAX && hf.d.content_size <= bound;
+      if (usable && hf.d.content_size > dst_cap[i]) {
+        hf.status = ZD_E_DST_TOO_SMALL;
+        hf.key = make_key(PH_LIMIT, 0, 0, 0, ZD_E_DST_TOO_SMALL);
+      }
+      bind[i] = !usable && dst_cap[i] < bound;
+    }
+    std::vector<HostPart> parts;
+    parts_from(kept, bl, parts);
+    P->set_parts(std::move(parts));
+  }
+  P->index_status = 0;
+  P->index_stop = P->nframes;
+  const auto t2 = std::chrono::steady_clock::now();
+
+  // ---- descriptors (host), placed at the chunks' destinations ----
+  {
+    const int32_t none[3] = {-1, -1, -1}, pre[3] = {0, 0, 0};
+    const uint64_t rep0[3] = {1, 4, 8};
+    const DictData* D = B->dict.get();
+    const int r = D ? build_plan(P, D->raw ? -1 : 0, D->raw ? none : pre, D->content, D->rep, 0, true)
+                    : build_plan(P, -1, none, 0, rep0, 0, true);
+    if (r) return r;
+  }
+  P->info.src_bytes = total;
+  const auto t3 = std::chrono::steady_clock::now();
+  if (int r = upload_desc(P)) return r;
+  if (int r = upload_dict_tables(P)) return r;
+  HIPCHK(hipMemcpy(B->d_bind, bind.data(), n, hipMemcpyHostToDevice));
+  if (!aux_take(P)) return ZD_E_HIP;
+  const auto t4 = std::chrono::steady_clock::now();
+  auto ns = [](auto a, auto b) {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count();
+  };
+  zd_batch_info& I = B->info;
+  I.gathered_bytes = total;
+  I.nblocks = P->info.nblocks;
+  I.nsequences = P->info.nsequences;
+  I.workspace_bytes = P->W.total + B->arr_bytes;
+  I.executors = P->info.executors;
+  I.gather_ns = ns(t0, t1);
+  I.walk_ns = ns(t1, t2);
+  I.host_ns = ns(t2, t3);
+  I.upload_ns = ns(t3, t4);
+  *out = hold.release();
+  return ZD_OK;
+}
+
+int zd_batch_info_get(const zd_batch* B, zd_batch_info* info) {
+  if (!B || !info) return ZD_E_INVALID_ARG;
+  *info = B->info;
+  return ZD_OK;
+}
+
+int zd_batch_decode_async(zd_batch* B, void* stream) {
+  if (!B) return ZD_E_INVALID_ARG;
+  if (!B->P) return ZD_OK;
+  const hipStream_t s = (hipStream_t)stream;
+  zd_plan* P = B->P;
+  // every frame at its own destination from the lowest one: never the plan's
+  // staging, and no capacity but the frames' own
+  if (int r = decode_launch(P, B->d_gather, B->outbase, s)) return r;
+  HIPCHK(launch_batch_results((const FrameState*)(P->d_ws + P->W.frame_state), B->d_bind, (uint32_t)B->n, B->d_status,
+                              B->d_len, s));
+  B->launched = true;
+  B->have_results = false;
+  return ZD_OK;
+}
+
+int zd_batch_device_results(const zd_batch* B, const int32_t** d_status, const uint64_t** d_len) {
+  if (!B) return ZD_E_INVALID_ARG;
+  if (d_status) *d_status = B->d_status;
+  if (d_len) *d_len = B->d_len;
+  return ZD_OK;
+}
+
+int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, size_t cap, uint64_t* nfailed) {
+  if (!B || ((status || len) && cap < B->n)) return ZD_E_INVALID_ARG;
+  if (nfailed) *nfailed = 0;
+  if (!B->P) return ZD_OK;
+  if (!B->launched) return ZD_E_INVALID_ARG;
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t n = B->n;
+  zd_plan* P = B->P;
+  HIPCHK(hipStreamSynchronize(s));
+  B->h_status.resize(n);
+  B->h_len.resize(n);
+  HIPCHK(hipMemcpy(B->h_status.data(), B->d_status, 4 * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(B->h_len.data(), B->d_len, 8 * n, hipMemcpyDeviceToHost));
+  if (P->n_jframes) {
+    // chunks whose pointer jumping did not converge within K4J's rounds: once
+    // more on the streaming executor, as an internal batch of just those
+    // chunks (from the gathered copies), then into the device arrays
+    std::vector<FrameState> st(n);
+    HIPCHK(hipMemcpy(st.data(), P->d_ws + P->W.frame_state, n * sizeof(FrameState), hipMemcpyDeviceToHost));
+    std::vector<size_t> redo;
+    for (size_t i = 0; i < n; i++) {
+      const uint64_t k = st[i].key;
+      if (key_code(k) == ZD_E_OUT_OF_DOMAIN && key_phase(k) == PH_LIMIT && key_stage(k) == LS_JROUNDS)
+        redo.push_back(i);
+    }
+    if (!redo.empty()) {
+      const size_t m = redo.size();
+      std::vector<const void*> src(m);
+      std::vector<void*> dst(m);
+      std::vector<uint64_t> sz(m), dc(m);
+      for (size_t k = 0; k < m; k++) {
+        const size_t i = redo[k];
+        src[k] = B->d_gather + B->goff[i];
+        sz[k] = B->src_size[i];
+        dst[k] = (void*)(uintptr_t)B->dst[i];
+        dc[k] = B->dst_cap[i];
+      }
+      const uint32_t flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_J_ONE_ROUND)) | ZD_F_FRAME_SERIAL;
+      zd_dict dh{B->dict};
+      zd_batch* Q = nullptr;
+      int r = zd_batch_create(src.data(), sz.data(), dst.data(), dc.data(), m, flags, B->dict ? &dh : nullptr, s, &Q);
+      if (r) return r;
+      std::vector<int32_t> st2(m);
+      std::vector<uint64_t> ln2(m);
+      r = zd_batch_decode_async(Q, s);
+      if (!r) r = zd_batch_results(Q, s, st2.data(), ln2.data(), m, nullptr);
+      zd_batch_destroy(Q);
+      if (r) return r;
+      for (size_t k = 0; k < m; k++) {
+        const size_t i = redo[k];
+        B->h_status[i] = st2[k];
+        B->h_len[i] = ln2[k];
+        HIPCHK(hipMemcpy(B->d_status + i, &st2[k], 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(B->d_len + i, &ln2[k], 8, hipMemcpyHostToDevice));
+      }
+    }
+  }
+  uint64_t bad = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (status) status[i] = B->h_status[i];
+    if (len) len[i] = B->h_len[i];
+    bad += B->h_status[i] != 0;
+  }
+  if (nfailed) *nfailed = bad;
+  B->have_results = true;
+  return ZD_OK;
+}
+
+int zd_batch_checksums(zd_batch* B, void* stream, int32_t* ok, uint64_t* hash) {
+  if (!B) return ZD_E_INVALID_ARG;
+  if (!B->P) return ZD_OK;
+  if (!B->launched) return ZD_E_INVALID_ARG;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!B->have_results)
+    if (int r = zd_batch_results(B, stream, nullptr, nullptr, 0, nullptr)) return r;
+  const size_t n = B->n;
+  std::vector<uint64_t> h(n);
+  HIPCHK(launch_xxh64(B->outbase, B->d_out, B->d_len, (uint32_t)n, B->d_hash, s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(h.data(), B->d_hash, 8 * n, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; i++) {
+    const zd_frame_desc& d = B->P->frame(i).d;
+    const bool done = B->h_status[i] == 0;
+    const bool have = done && d.kind == ZD_FRAME_ZSTD && d.has_checksum;
+    if (ok) ok[i] = have ? ((uint32_t)h[i] == d.checksum ? 1 : 0) : -1;
+    if (hash) hash[i] = done ? h[i] : 0;
+  }
+  return ZD_OK;
 }
 
 // ===========================================================================

@@ -6281,4 +6281,108 @@ hipError_t launch_walk(const uint8_t* src, uint64_t n, uint64_t first, uint64_t 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Batches of scattered chunks (zd_batch_create).
+//
+// zd_k_gather copies the chunks into the batch's own buffer, where the
+// bitstream readers may fetch windows below a stream's first byte and
+// ZD_SRC_PADDING past the input's end (winu_load, seq_chainl) as inside any
+// one input.  Pieces as K0's: a piece of <= 32 KiB takes K0_SPLIT workgroups
+// of 256 threads, one 16-byte chunk per thread; a chunk's copy starts 16-byte
+// aligned, so the stores are aligned and the loads take the source's own
+// alignment; the tail is copied bytewise by the piece's first workgroup, which
+// for a chunk's last piece also zeroes the bytes up to the next chunk's copy.
+// Nothing outside [src, src + size) is read.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void zd_k_gather(ChunkList L, uint8_t* gathered,
+                                                   const GatherPiece* __restrict__ pieces) {
+  const uint32_t sub = blockIdx.x % K0_SPLIT;
+  const GatherPiece p = pieces[blockIdx.x / K0_SPLIT];
+  const uint64_t size = L.size[p.chunk], at = (uint64_t)p.piece * COPY_PIECE;
+  const uint32_t n = (uint32_t)min((uint64_t)COPY_PIECE, size - at);     // (at <= size: the host's piece list)
+  const uint8_t* s = (const uint8_t*)(uintptr_t)L.src[p.chunk] + at;
+  uint8_t* d = gathered + L.off[p.chunk] + at;
+  const int t = threadIdx.x;
+  const uint32_t x = 16 * (256 * sub + (uint32_t)t);
+  if (x + 16 <= n) *(g_u32x4*)(d + x) = ldg16(s + x);
+  if (sub == 0) {
+    const uint32_t tail0 = n & ~15u;
+    if (tail0 + t < n) d[tail0 + t] = s[tail0 + t];
+    // the chunk's end: zero bytes to the next chunk's copy (at align16(size) + ZD_SRC_PADDING)
+    if (at + n == size) {
+      const uint32_t pad = (uint32_t)(((size + 15) & ~15ull) + ZD_SRC_PADDING - size);
+      if ((uint32_t)t < pad) d[n + t] = 0;
+    }
+  }
+}
+
+hipError_t launch_gather(const ChunkList& L, uint8_t* gathered, const GatherPiece* d_pieces, uint64_t npieces,
+                         hipStream_t s) {
+  if (!npieces) return hipSuccess;
+  hipLaunchKernelGGL(zd_k_gather, dim3((uint32_t)(npieces * K0_SPLIT)), dim3(256), 0, s, L, gathered, d_pieces);
+  return hipGetLastError();
+}
+
+// zd_k_walk_chunks: the header walk of a batch's chunks in the gathered
+// buffer (zd_walk.h index_chunk, bounded by each chunk's own size), one lane
+// per chunk, 64 chunks a wave.  Count pass: the blocks each chunk's walk
+// keeps; fill pass: one HostFrame per chunk and its blocks at b_off[i].
+template <bool FILL>
+__global__ __launch_bounds__(64) void zd_k_walk_chunks(const uint8_t* __restrict__ gathered, ChunkList L, uint32_t n,
+                                                      bool rfc_empty_lits, uint32_t* nblocks,
+                                                      const uint64_t* __restrict__ b_off, HostFrame* frames,
+                                                      HostBlock* blocks) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  Bytes in{gathered + L.off[i], (size_t)L.size[i]};
+  HostFrame hf;
+  if (FILL) {
+    WalkFill sink{blocks, b_off[i]};
+    index_chunk(gathered, in, &hf, sink, rfc_empty_lits);
+    frames[i] = hf;
+  } else {
+    WalkCount sink;
+    index_chunk(gathered, in, &hf, sink, rfc_empty_lits);
+    nblocks[i] = sink.n;
+  }
+}
+
+hipError_t launch_walk_chunks(const uint8_t* gathered, const ChunkList& L, uint32_t n, bool rfc_empty_lits,
+                              uint32_t* nblocks, const uint64_t* b_off, HostFrame* frames, HostBlock* blocks, bool fill,
+                              hipStream_t s) {
+  if (!n) return hipSuccess;
+  const dim3 grid((n + 63) / 64);
+  if (fill)
+    hipLaunchKernelGGL(zd_k_walk_chunks<true>, grid, dim3(64), 0, s, gathered, L, n, rfc_empty_lits, nblocks, b_off,
+                       frames, blocks);
+  else
+    hipLaunchKernelGGL(zd_k_walk_chunks<false>, grid, dim3(64), 0, s, gathered, L, n, rfc_empty_lits, nblocks, b_off,
+                       frames, blocks);
+  return hipGetLastError();
+}
+
+// zd_k_batch_results: the batch's device result arrays, the last launch of
+// zd_batch_decode_async.  A frame that reached its capacity while decoding
+// (LS_CAPACITY) where the caller's dst_cap was the binding limit is
+// ZD_E_DST_TOO_SMALL; every other status is the frame key's own code.
+__global__ __launch_bounds__(256) void zd_k_batch_results(const FrameState* __restrict__ fstate,
+                                                          const uint8_t* __restrict__ bind, uint32_t n,
+                                                          int32_t* status, uint64_t* len) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t k = fstate[i].key;
+  int code = key_code(k);
+  if (code == ZD_E_OUT_OF_DOMAIN && key_phase(k) == PH_LIMIT && key_stage(k) == LS_CAPACITY && bind[i])
+    code = ZD_E_DST_TOO_SMALL;
+  status[i] = code;
+  len[i] = code ? 0 : fstate[i].out_len;
+}
+
+hipError_t launch_batch_results(const FrameState* fstate, const uint8_t* bind, uint32_t n, int32_t* status,
+                                uint64_t* len, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(zd_k_batch_results, dim3((n + 255) / 256), dim3(256), 0, s, fstate, bind, n, status, len);
+  return hipGetLastError();
+}
+
 }  // namespace zd

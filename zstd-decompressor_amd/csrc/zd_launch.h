@@ -93,6 +93,31 @@ hipError_t launch_plan_count(const PlanCtx& X, const HostFrame* frames, const Ho
 hipError_t launch_plan_fill(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
                             const uint64_t* cnt, const uint64_t* tot, const Sink& S, hipStream_t s);
 
+// A batch's chunks (zd_batch_create), device arrays of n entries: where chunk
+// i lies (src, size) and where its copy sits in the gathered buffer (off, a
+// multiple of 16; the copy is followed by zero bytes up to the next chunk's).
+struct ChunkList {
+  const uint64_t* src;     // device addresses
+  const uint64_t* size;
+  const uint64_t* off;
+};
+// One piece (<= COPY_PIECE bytes) of a chunk, zd_k_gather's unit of work
+struct GatherPiece { uint32_t chunk, piece; };
+// zd_k_gather: the chunks' bytes into the gathered buffer, piece by piece.
+hipError_t launch_gather(const ChunkList& L, uint8_t* gathered, const GatherPiece* d_pieces, uint64_t npieces,
+                         hipStream_t s);
+// zd_k_walk_chunks: one lane per chunk of the gathered buffer.  Count pass
+// (fill = false): nblocks[i] = the blocks chunk i's walk keeps; fill pass:
+// frames[i] and its blocks at blocks[b_off[i]...] (block indices global).
+hipError_t launch_walk_chunks(const uint8_t* gathered, const ChunkList& L, uint32_t n, bool rfc_empty_lits,
+                              uint32_t* nblocks, const uint64_t* b_off, HostFrame* frames, HostBlock* blocks, bool fill,
+                              hipStream_t s);
+// zd_k_batch_results: chunk i's status and length from frame i's state (bind[i]:
+// the caller's capacity is the frame's binding limit, so reaching it is
+// ZD_E_DST_TOO_SMALL).
+hipError_t launch_batch_results(const FrameState* fstate, const uint8_t* bind, uint32_t n, int32_t* status,
+                                uint64_t* len, hipStream_t s);
+
 constexpr int N_KERNELS = 6;
 // mode-2 launch groups (LaunchArgs::dom_events: events 2g, 2g + 1)
 constexpr int N_DOM = 5;

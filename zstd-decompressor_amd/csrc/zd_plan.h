@@ -74,6 +74,12 @@ struct PlanCtx {
   // frame's own bytes).  dict_id: the dictionary's ID (0: raw content).
   bool dict;
   uint32_t dict_id;
+  // Optional per-frame placement (a batch, zd_batch_create; null everywhere
+  // else, the device planner included): frame fi's output starts at
+  // place_out[fi] from the output base instead of the running offset, and its
+  // capacity is at most place_cap[fi].
+  const uint64_t* place_out;
+  const uint64_t* place_cap;
 };
 
 // Where the filling pass writes: the plan's host vectors (small plans, the
@@ -227,7 +233,12 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
     cap = X.cap0;
     c.inexact = 1;
   }
-  fd.out = c.out;
+  uint64_t out = c.out;
+  if (X.place_out) {
+    out = X.place_out[fi];
+    cap = plan_min(cap, X.place_cap[fi]);
+  }
+  fd.out = out;
   fd.out_cap = cap;
   // K4J: frames of many compressed blocks, and any frame past the streaming
   // K4's int32 positions (distances, zd_common.h)
@@ -295,7 +306,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
         if (FILL) {
           CopyDesc cd{};
           cd.src = hb.src + (hb.type == 1 ? 0 : x);
-          cd.dst = c.out + own0 + pre + x;
+          cd.dst = out + own0 + pre + x;
           cd.size = (uint32_t)plan_min<uint64_t>(COPY_PIECE, hb.size - x);
           cd.fill = hb.type == 1 ? (0x100u | hb.rle) : 0u;
           S.copies[c.copies] = cd;
@@ -315,7 +326,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
     }
   }
   if (FILL) {
-    S.frame_out[fi] = c.out;
+    S.frame_out[fi] = out;
     S.frame_cap[fi] = cap;
     S.fdesc[fi] = fd;
     S.fstate0[fi] = fs;

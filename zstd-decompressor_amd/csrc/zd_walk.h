@@ -316,6 +316,57 @@ ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK
   return 0;
 }
 
+// A block sink that keeps nothing (the frames of a chunk that are walked only
+// to be stepped over)
+struct NoBlocks {
+  ZD_HD size_t size() const { return 0; }
+  ZD_HD void push(const HostBlock&) {}
+};
+
+// Walks one chunk of a batch (zd_batch_create): `in` is the chunk, bounded by
+// its own size.  A chunk is any number of skippable frames around exactly one
+// zstd frame; that frame is indexed into *hf with its blocks in S, the
+// skippable frames are stepped over.  A chunk without a zstd frame (no bytes,
+// or skippable frames only) leaves *hf a frame of no blocks and no output.
+// A chunk the walk cannot consume entirely this way fails as a whole -- the
+// frame's own parse error, the walk's status at the bytes it stopped at
+// (trailing bytes, a truncated frame), ZD_E_OUT_OF_DOMAIN at a second zstd
+// frame -- and travels as hf->key, the route of a frame that fails to index.
+template <typename SINK>
+ZD_HD inline int index_chunk(const uint8_t* base, Bytes& in, HostFrame* hf, SINK& S, bool rfc_empty_lits = false) {
+  zero_bytes(&hf->d, sizeof hf->d);
+  hf->d.src_offset = (uint64_t)(in.p - base);
+  hf->d.content_size = UINT64_MAX;
+  hf->d.dict_id = UINT64_MAX;
+  hf->d.kind = ZD_FRAME_SKIPPABLE;
+  hf->b0 = (uint32_t)S.size();
+  hf->nb = 0;
+  hf->ncomp = 0;
+  hf->key = KEY_NONE;
+  hf->status = 0;
+  bool have = false;
+  auto fail = [&](int code) {
+    hf->status = code;
+    hf->key = make_key(PH_PARSE, 0, PS_STRUCT, 0, code);
+    return code;
+  };
+  while (in.n) {
+    const bool zstd = in.n >= 4 && ((uint32_t)in.p[0] | ((uint32_t)in.p[1] << 8) | ((uint32_t)in.p[2] << 16) |
+                                    ((uint32_t)in.p[3] << 24)) == MAGIC_ZSTD;
+    if (zstd) {
+      if (have) return fail(ZD_E_OUT_OF_DOMAIN);
+      if (int r = index_frame(base, in, hf, S, rfc_empty_lits)) return r;
+      have = true;
+    } else {
+      // a skippable frame, or the walk's own failure (bytes that are no frame)
+      HostFrame skip;
+      NoBlocks none;
+      if (int r = index_frame(base, in, &skip, none, rfc_empty_lits)) return fail(r);
+    }
+  }
+  return 0;
+}
+
 ZD_HD inline bool magic_word(uint32_t m) { return m == MAGIC_ZSTD || (m ^ MAGIC_SKIP) <= 0x0F; }
 
 // The device walk's per-range summary (zd_k_walk, count pass): where the

@@ -7,7 +7,8 @@ Module map (reference -> here):
   block.rs            -> block         Block.parse / Block.decode(ctx)
   decoding_context.rs -> decoding_context  DecodingContext (GPU-resident)
   decoders/, literals.rs, sequences.rs -> HIP kernels behind the C ABI (include/zd.h)
-Batch API (the hot path): batch.decompress / batch.Plan.
+Batch API (the hot path): batch.decompress / batch.Plan; batch.Batch for
+scattered device chunks with per-chunk buffers and statuses.
 """
 from . import _lib
 from ._lib import ZdError
@@ -15,7 +16,8 @@ from .parsing import ForwardByteParser
 from .frame import Frame, FrameIterator, Header, Skippable, ZStandard, MAX_WIN_SIZE
 from .block import Block
 from .decoding_context import DecodingContext
-from .batch import Dictionary, Plan, decompress, frames_index
+from .batch import Batch, Dictionary, Plan, decode_tensors, decompress, frames_index
 
 __all__ = ["ZdError", "ForwardByteParser", "Frame", "FrameIterator", "Header", "Skippable", "ZStandard",
-           "MAX_WIN_SIZE", "Block", "DecodingContext", "Dictionary", "Plan", "decompress", "frames_index"]
+           "MAX_WIN_SIZE", "Block", "DecodingContext", "Batch", "Dictionary", "Plan", "decode_tensors", "decompress",
+           "frames_index"]

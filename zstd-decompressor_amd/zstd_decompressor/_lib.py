@@ -54,6 +54,13 @@ class GatherResult(C.Structure):
                 ("first_error_frame", C.c_int64)]
 
 
+class BatchInfo(C.Structure):
+    _fields_ = [("nchunks", C.c_uint64), ("gathered_bytes", C.c_uint64), ("nblocks", C.c_uint64),
+                ("nsequences", C.c_uint64), ("workspace_bytes", C.c_uint64), ("executors", C.c_uint32),
+                ("reserved", C.c_uint32), ("gather_ns", C.c_uint64), ("walk_ns", C.c_uint64),
+                ("host_ns", C.c_uint64), ("upload_ns", C.c_uint64)]
+
+
 COMM_ID_BYTES = 128
 
 # every entry point declared in include/zd.h: name -> (restype, argtypes)
@@ -84,6 +91,15 @@ SIGNATURES = {
                                C.POINTER(C.c_int)]),
     "zd_plan_create_dict": (C.c_int, [_vp, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
     "zd_decompress_dict": (C.c_int, [_vp, _sz, _vp, _sz, _szp, C.c_uint32, _vp]),
+    "zd_batch_create": (C.c_int, [C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64), _sz,
+                                  C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
+    "zd_batch_info_get": (C.c_int, [_vp, C.POINTER(BatchInfo)]),
+    "zd_batch_decode_async": (C.c_int, [_vp, _vp]),
+    "zd_batch_device_results": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "zd_batch_results": (C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _sz,
+                                   C.POINTER(C.c_uint64)]),
+    "zd_batch_checksums": (C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    "zd_batch_destroy": (None, [_vp]),
     "zd_context_new": (C.c_int, [C.c_uint64, C.POINTER(_vp)]),
     "zd_context_free": (None, [_vp]),
     "zd_block_decode": (C.c_int, [_vp, _vp, _sz, _szp, C.POINTER(C.c_int)]),

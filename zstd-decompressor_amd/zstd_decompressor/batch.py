@@ -2,7 +2,8 @@
 
 `decompress` mirrors the CLI loop (src/main.rs:43-58) on host buffers;
 `Plan` keeps input/output in HBM (torch tensors or raw device pointers) and is
-what bench.py times.
+what bench.py times; `Batch` decodes N chunks held at N device addresses, each
+into its own device buffer with its own status (zd_batch, include/zd.h).
 """
 from __future__ import annotations
 
@@ -210,3 +211,102 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+def _u64_array(values, n: int):
+    """n integers as a ctypes uint64 array (array.array packs a list far faster
+    than ctypes' own constructor: 65,536 chunks in a millisecond or two)."""
+    import array
+    try:
+        a = array.array("Q", values)                            # plain ints
+    except TypeError:
+        a = array.array("Q", [int(v or 0) for v in values])     # None for a null pointer, numpy scalars
+    return (C.c_uint64 * n).from_buffer(a) if n else (C.c_uint64 * 1)()
+
+
+class Batch:
+    """zd_batch: N independently compressed chunks at N device addresses, each
+    decoded into its own device buffer with its own status.
+
+    src_ptrs / dst_ptrs are device addresses (integers, e.g. tensor.data_ptr()),
+    src_sizes / dst_caps byte counts.  A chunk holds one zstd frame (skippable
+    frames around it are skipped).  The sources are copied at creation (they
+    need no padding and may be released afterwards); the destinations must
+    stay valid while the batch decodes."""
+
+    def __init__(self, src_ptrs, src_sizes, dst_ptrs, dst_caps, flags: int = 0, dictionary=None, stream: int = 0):
+        n = len(src_ptrs)
+        if not (len(src_sizes) == len(dst_ptrs) == len(dst_caps) == n):
+            raise ValueError("src_ptrs, src_sizes, dst_ptrs and dst_caps differ in length")
+        if dictionary is not None and not getattr(dictionary, "_h", None):
+            raise ValueError("the Dictionary is closed")
+        sp, ss, dp, dc = (_u64_array(v, n) for v in (src_ptrs, src_sizes, dst_ptrs, dst_caps))
+        vpp = C.POINTER(C.c_void_p)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().zd_batch_create(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, n, flags,
+                                              dictionary._h if dictionary else None, C.c_void_p(stream), C.byref(h)),
+                   "zd_batch_create")
+        self._h = h
+        self.nchunks = n
+        self.info = _lib.BatchInfo()
+        _lib.check(_lib.lib().zd_batch_info_get(h, C.byref(self.info)), "zd_batch_info_get")
+
+    def decode_async(self, stream: int = 0):
+        """Launch the decode of every chunk (no allocation, no host synchronisation)."""
+        _lib.check(_lib.lib().zd_batch_decode_async(self._h, C.c_void_p(stream)), "zd_batch_decode_async")
+
+    def device_results(self):
+        """(device address of the int32 statuses, device address of the uint64
+        lengths): written by the last kernel decode_async queues."""
+        st, ln = C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.lib().zd_batch_device_results(self._h, C.byref(st), C.byref(ln)), "zd_batch_device_results")
+        return st.value or 0, ln.value or 0
+
+    def results(self, stream: int = 0):
+        """(statuses, lengths) per chunk, after waiting for `stream`."""
+        n = self.nchunks
+        st = (C.c_int32 * max(n, 1))()
+        ln = (C.c_uint64 * max(n, 1))()
+        bad = C.c_uint64()
+        _lib.check(_lib.lib().zd_batch_results(self._h, C.c_void_p(stream), st, ln, n, C.byref(bad)),
+                   "zd_batch_results")
+        return list(st)[:n], list(ln)[:n]
+
+    def checksums(self, stream: int = 0):
+        """(ok per chunk: 1 match / 0 mismatch / -1 none or not decoded, XXH64 digests)."""
+        n = self.nchunks
+        ok = (C.c_int32 * max(n, 1))()
+        h = (C.c_uint64 * max(n, 1))()
+        _lib.check(_lib.lib().zd_batch_checksums(self._h, C.c_void_p(stream), ok, h), "zd_batch_checksums")
+        return list(ok)[:n], list(h)[:n]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().zd_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decode_tensors(srcs, dsts, dictionary=None, flags: int = 0):
+    """Decode uint8 device tensors srcs[i] (one chunk each) into dsts[i] on
+    torch's current stream: (statuses, lengths)."""
+    import torch
+    if len(srcs) != len(dsts):
+        raise ValueError("srcs and dsts differ in length")
+    for t in list(srcs) + list(dsts):
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("contiguous uint8 device tensors required")
+    stream = torch.cuda.current_stream().cuda_stream
+    b = Batch([t.data_ptr() if t.numel() else 0 for t in srcs], [t.numel() for t in srcs],
+              [t.data_ptr() if t.numel() else 0 for t in dsts], [t.numel() for t in dsts],
+              flags=flags, dictionary=dictionary, stream=stream)
+    try:
+        b.decode_async(stream)
+        return b.results(stream)
+    finally:
+        b.close()
