@@ -76,7 +76,8 @@ extern "C" {
 #define ZD_E_COMM            (-97) /* an RCCL call failed, or RCCL is not loadable */
 #define ZD_E_DICT_CORRUPTED  (-98) /* zd_dict_create: a formatted dictionary truncated before its content, with
                                       a repeat offset of 0 or past the content, or without content */
-#define ZD_E_DICT_MISMATCH   (-99) /* a frame names a Dictionary_ID other than the plan's dictionary's */
+#define ZD_E_DICT_MISMATCH   (-99) /* a frame names a Dictionary_ID other than the plan's dictionary's
+                                      (a dictionary set: an ID the set does not hold) */
 
 /* Device workspaces of destroyed plans are kept for reuse by later plans of
  * the process (bounded by ZD_WS_CACHE_MB, default 8 GiB; 0 disables it).
@@ -385,6 +386,63 @@ int  zd_plan_create_dict(const uint8_t* src, size_t n, uint32_t flags, const zd_
 int  zd_decompress_dict(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len,
                         uint32_t flags, const zd_dict* dict);
 
+/* Dictionary sets (libzstd: ZSTD_d_refMultipleDDicts): many dictionaries in
+ * one plan or batch, each frame choosing its own by the Dictionary_ID in its
+ * header -- one dictionary per column, table or message type, and records
+ * without any, decoded together instead of one plan per dictionary.
+ *
+ * zd_dict_set_create: ndicts >= 1 dictionaries made by zd_dict_create on the
+ * current device.  fallback: index of the dictionary for frames that carry no
+ * Dictionary_ID (or ID 0), or -1: such frames decode with no dictionary,
+ * exactly as in a plan made without one.  The set shares ownership of its
+ * dictionaries' device data (the zd_dict handles may be destroyed at once),
+ * plans and batches share ownership of the set: any order of destroy calls is
+ * legal.  The call allocates 32 bytes of device memory and copies nothing.
+ * ZD_E_INVALID_ARG, before any HIP call: a NULL argument, ndicts == 0 or above
+ * ZD_DICT_SET_MAX, a NULL or destroyed entry, fallback outside [-1, ndicts),
+ * two entries with the same ID, a dictionary of ID 0 (raw content) anywhere
+ * but at `fallback` (no frame can name it), dictionaries of different
+ * devices; and a set made on another device than the current one.
+ * ZD_DICT_SET_MAX bounds what one plan can be made to pay for its
+ * dictionaries: a plan keeps tables (a Huffman and an FSE slot, about 11 KiB,
+ * filled by three small copies at creation) for every formatted dictionary
+ * that one of ITS frames uses, at most 4096 x 11 KiB = 44 MiB and 12,288
+ * copies; dictionaries of the set that no frame of the plan names cost it
+ * nothing. */
+typedef struct zd_dict_set zd_dict_set;
+#define ZD_DICT_SET_MAX 4096
+int  zd_dict_set_create(const zd_dict* const* dicts, size_t ndicts, int fallback, zd_dict_set** out);
+/* Legal before the plans / batches made with it are destroyed. */
+void zd_dict_set_destroy(zd_dict_set* set);
+/* ndicts and fallback as given to zd_dict_set_create.  Either pointer may be NULL. */
+int  zd_dict_set_info(const zd_dict_set* set, size_t* ndicts, int* fallback);
+/* zd_plan_create with a dictionary set.  A zstd frame with a non-zero
+ * Dictionary_ID decodes with the set's dictionary of that ID, as in
+ * zd_plan_create_dict (tables, repeat offsets, content); when the set holds
+ * none, the frame gets ZD_E_DICT_MISMATCH and the plan stops there like at
+ * any failing frame (ZD_E_NOT_DECODED after it).  A frame without an ID, or
+ * with ID 0, decodes with the fallback dictionary; with fallback -1 with none:
+ * first repeat offsets 1, 4, 8, no previous tables, a match before the
+ * frame's start is ZD_E_IMPOSSIBLE_VALUE -- the bytes and status a plain plan
+ * gives it.  The relaxation of zd_plan_create_dict (a Raw literals section of
+ * 0 bytes is accepted) is plan-wide: it holds for every frame of the plan, the
+ * ones that decode without a dictionary included.  A set of one dictionary
+ * with fallback 0 gives the bytes and statuses of zd_plan_create_dict.  A frame
+ * that zd_plan_decompress plans again (capacity) keeps its own dictionary.
+ * Limits, as in zd_plan_create_dict and for every frame of the plan, the ones
+ * without a dictionary included: the streaming executor only -- never the
+ * fused kernel, K4F or K4J, ZD_F_BLOCK_PARALLEL is ignored and
+ * zd_plan_info.executors is 0; a frame whose own dictionary's content plus
+ * capacity passes the streaming executor's int32 positions is
+ * ZD_E_OUT_OF_DOMAIN.  zd_plan_info.ncompressed does not count the
+ * dictionaries' tables.  zd_plan_create_device, the sharded calls and
+ * zd_context take no set.  ZD_E_INVALID_ARG: a NULL or destroyed set, or one
+ * made on another device than the current one. */
+int  zd_plan_create_dicts(const uint8_t* src, size_t n, uint32_t flags, const zd_dict_set* set, zd_plan** out);
+/* zd_decompress with a dictionary set (set must not be NULL). */
+int  zd_decompress_dicts(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len,
+                         uint32_t flags, const zd_dict_set* set);
+
 /* ------------------------------------------------------------------ */
 /* Batches of scattered chunks (beyond the reference, whose input is    */
 /* one byte range of frames): N independently compressed chunks at N    */
@@ -442,6 +500,15 @@ typedef struct zd_batch_info {
 int  zd_batch_create(const void* const* d_src, const uint64_t* src_bytes,
                      void* const* d_dst, const uint64_t* dst_cap, size_t nchunks,
                      uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out);
+/* zd_batch_create with a dictionary set (must not be NULL) in place of the one
+ * dictionary: every chunk's frame chooses its dictionary as in
+ * zd_plan_create_dicts, under its limits; a chunk whose frame names an ID the
+ * set does not hold is ZD_E_DICT_MISMATCH, alone.  The other arguments, checks
+ * and costs are zd_batch_create's; a set made on another device than the
+ * current one is ZD_E_INVALID_ARG. */
+int  zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes,
+                           void* const* d_dst, const uint64_t* dst_cap, size_t nchunks,
+                           uint32_t flags, const zd_dict_set* set, void* stream, zd_batch** out);
 int  zd_batch_info_get(const zd_batch* batch, zd_batch_info* info);
 /* Launches the decode of every chunk on `stream`, ending with a kernel that
  * writes the batch's device result arrays (zd_batch_device_results).  No

@@ -484,6 +484,9 @@ struct Workspace {
   uint64_t jst;                                         // K4J per-byte state words
   uint64_t redo, k2done;                                // zd_k_fused: frames for the redo pass, K2's finished workgroups
   uint64_t hframes;                                     // device-built plans: the walk's frame index (zd_walk.h HostFrame)
+  // dictionary-set plans only (0 elsewhere): u32 per frame, the frame's entry in dict_ptrs (zd_plan.h
+  // Sink::frame_dict); the used dictionaries' content addresses and, last, the address no-dictionary frames get
+  uint64_t frame_dict, dict_ptrs;
   uint64_t total;
 };
 

@@ -80,6 +80,39 @@ struct DictData {
 struct zd_dict {
   std::shared_ptr<DictData> p;
 };
+// Dictionary set (zd_dict_set_create): the dictionaries sorted by ID (a
+// raw-content one, ID 0, only ever the fallback), shared by the zd_dict_set
+// handle and every plan and batch made with it.
+namespace {
+struct DictSetData {
+  int dev = -1;
+  std::vector<std::shared_ptr<DictData>> d;   // sorted by ID
+  int fallback = -1;                          // index into d, or -1
+  int fallback_arg = -1;                      // as given to zd_dict_set_create
+  // what a frame without a dictionary gets for one: DICT_PAD zero bytes on
+  // both sides of d_none (its positions [0, 0) are never read, the window
+  // preload reads up to 15 bytes below and 1 byte above it)
+  uint8_t* d_none_buf = nullptr;
+  ~DictSetData() {
+    if (d_none_buf) (void)hipFree(d_none_buf);
+  }
+  const uint8_t* d_none() const { return d_none_buf + DICT_PAD; }
+  // the set's dictionary of a frame: by its Dictionary_ID, else the fallback; -1: none
+  int find(const zd_frame_desc& f) const {
+    if (f.kind != ZD_FRAME_ZSTD) return -1;
+    if (f.dict_id == UINT64_MAX || f.dict_id == 0) return fallback;
+    size_t lo = 0, hi = d.size();
+    while (lo < hi) {
+      const size_t m = lo + (hi - lo) / 2;
+      if (d[m]->id < f.dict_id) lo = m + 1; else hi = m;
+    }
+    return (lo < d.size() && d[lo]->id == f.dict_id) ? (int)lo : -1;
+  }
+};
+}  // namespace
+struct zd_dict_set {
+  std::shared_ptr<DictSetData> p;
+};
 
 // ===========================================================================
 // Plan
@@ -87,6 +120,18 @@ struct zd_dict {
 struct zd_plan {
   uint32_t flags = 0;
   std::shared_ptr<DictData> dict;       // a dictionary plan (zd_plan_create_dict): kept alive by the plan
+  // a dictionary-set plan (zd_plan_create_dicts; never with `dict`): the set,
+  // and the dictionaries this plan's frames use -- PlanCtx::dset, sorted by ID,
+  // entry k's tables the prebuilt comp PlanDict::comp (the formatted ones
+  // are comps 0..n_dict_comps-1) and its content address dict_ptrs[k]; the
+  // last of dict_ptrs is the address of frames without a dictionary
+  std::shared_ptr<DictSetData> dset;
+  std::vector<PlanDict> dset_tab;
+  std::vector<const DictData*> dset_used;
+  int32_t dset_fallback = -1;
+  uint32_t n_dict_comps = 0;            // prebuilt comps at the head of the plan (a dictionary plan: 0 or 1)
+  std::vector<uint32_t> frame_dict;     // Sink::frame_dict of a plan that is not staged
+  bool with_dict() const { return dict != nullptr || dset != nullptr; }
   std::vector<HostPart> parts;          // the host walk's frames, in input order
   std::vector<size_t> part_f0;          // plan frame index of each part's first frame
   size_t nframes = 0;
@@ -402,8 +447,17 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   for (const HostPart& hp : P->parts)
     if (!hp.frames.empty()) { X.cap0_frame = hp.frames.data(); break; }
   X.flags = P->flags;
-  X.dict = P->dict != nullptr;
+  X.dict = P->with_dict();
   X.dict_id = P->dict ? P->dict->id : 0;
+  if (P->dset) {
+    // (never null in a set plan, whose workspace carries the per-frame table
+    // and whose K4 reads it: a plan none of whose frames uses a dictionary has
+    // an empty table, and an empty vector's data() may be null)
+    static const PlanDict no_entry{};
+    X.dset = P->dset_tab.empty() ? &no_entry : P->dset_tab.data();
+    X.ndset = (uint32_t)P->dset_tab.size();
+    X.dset_fallback = P->dset_fallback;
+  }
   X.place_out = P->place_out.empty() ? nullptr : P->place_out.data();
   X.place_cap = P->place_out.empty() ? nullptr : P->place_cap.data();
   RouteIn in{};
@@ -498,7 +552,7 @@ void plan_info(zd_plan* P, const PlanCounts& T) {
   zd_plan_info& I = P->info;
   I.nframes = T.frames;
   I.nblocks = T.blocks;
-  I.ncompressed = T.comps - ((P->dict && !P->dict->raw) ? 1 : 0);   // (not the dictionary's prebuilt comp)
+  I.ncompressed = T.comps - P->n_dict_comps;   // (not the dictionaries' prebuilt comps)
   I.out_bytes = T.out;
   I.out_exact = T.exact();
   I.workspace_bytes = P->W.total;
@@ -527,15 +581,42 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
     for (const HostPart& hp : P->parts)
       for (const HostFrame& hf : hp.frames) j_candidates += hf.key == KEY_NONE && hf.ncomp >= k4j_min;
   }
+  // a formatted dictionary's tables: the plan-level prebuilt comp 0 with LUT
+  // slot 0 and FSE slot 0, before every frame's (X.prev_huf / X.prev_tab name
+  // it); a dictionary set: one such comp per formatted dictionary that a frame
+  // of this plan uses, comps 0..U-1 with LUT and FSE slots 0..U-1
+  P->n_dict_comps = (P->dict && !P->dict->raw) ? 1u : 0u;
+  if (P->dset) {
+    const DictSetData& D = *P->dset;
+    std::vector<uint8_t> used(D.d.size(), 0);
+    for (const HostPart& hp : P->parts)
+      for (const HostFrame& hf : hp.frames) {
+        const int k = D.find(hf.d);
+        if (k >= 0) used[(size_t)k] = 1;
+      }
+    P->dset_tab.clear();
+    P->dset_used.clear();
+    P->dset_fallback = -1;
+    for (size_t k = 0; k < D.d.size(); k++) {
+      if (!used[k]) continue;
+      const DictData& dd = *D.d[k];
+      PlanDict e{};
+      e.dict_id = dd.id;
+      e.comp = dd.raw ? -1 : (int32_t)P->n_dict_comps++;
+      e.content = dd.content;
+      for (int q = 0; q < 3; q++) e.rep[q] = dd.rep[q];
+      if ((int)k == D.fallback) P->dset_fallback = (int32_t)P->dset_tab.size();
+      P->dset_tab.push_back(e);
+      P->dset_used.push_back(&dd);
+    }
+  }
   const PlanCtx X = plan_ctx(P, prev_huf, prev_tab, out_len0, rep0, fixed_cap, host_single_block_frames(P),
                              j_candidates);
 
   const size_t np = P->parts.size();
   std::vector<PlanCounts> cnt(np + 1);
-  // a formatted dictionary's tables: the plan-level prebuilt comp 0 with LUT
-  // slot 0 and FSE slot 0, before every frame's (X.prev_huf / X.prev_tab name it)
-  const bool dict_comp = P->dict && !P->dict->raw;
-  if (dict_comp) cnt[0].comps = cnt[0].luts = cnt[0].fses = 1;
+  const uint32_t dict_comps = P->n_dict_comps;
+  cnt[0].comps = cnt[0].luts = cnt[0].fses = dict_comps;
   const Sink none{};
   run_parts(np, [&](size_t k) {
     const HostPart& hp = P->parts[k];
@@ -560,6 +641,10 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
   W = Workspace{};
   uint64_t o = 0;
   carve_head(W, T, o);
+  if (X.dset) {
+    W.frame_dict = o; o = align_up(o + 4 * std::max<uint64_t>(T.frames, 1), 256);
+    W.dict_ptrs = o; o = align_up(o + 8 * (uint64_t)(X.ndset + 1), 256);
+  }
   P->desc_bytes = o;
   plan_totals(P, T, X.fused);
   P->frame_out.resize(T.frames);
@@ -585,7 +670,14 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
     S = Sink{(CompBlock*)(b + W.comp), (BlockRec*)(b + W.blocks), (FrameDesc*)(b + W.frames),
              (FrameState*)(b + W.frame_state0), (uint32_t*)(b + W.list_tables), (uint32_t*)(b + W.list_huf),
              (uint32_t*)(b + W.list_seq), (uint32_t*)(b + W.list_k4f), (CopyDesc*)(b + W.copies),
-             (JFrame*)(b + W.jframes), (JBlkDesc*)(b + W.jblkd), (JSegDesc*)(b + W.jsegd), nullptr, nullptr};
+             (JFrame*)(b + W.jframes), (JBlkDesc*)(b + W.jblkd), (JSegDesc*)(b + W.jsegd), nullptr, nullptr,
+             X.dset ? (uint32_t*)(b + W.frame_dict) : nullptr};
+    if (X.dset) {
+      const uint8_t** dp = (const uint8_t**)(b + W.dict_ptrs);
+      for (uint32_t k = 0; k < X.ndset; k++) dp[k] = P->dset_used[k]->d_content;
+      dp[X.ndset] = P->dset->d_none();
+    }
+    P->frame_dict.clear();
     P->comps.clear(); P->blocks.clear(); P->fdesc.clear(); P->fstate0.clear();
     P->list_tables.clear(); P->list_huf.clear(); P->list_seq.clear(); P->list_k4f.clear(); P->copies.clear();
     P->jframes.clear(); P->jblkd.clear(); P->jsegd.clear();
@@ -604,7 +696,9 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
     P->jsegd.assign(T.jseg, JSegDesc{});
     S = Sink{P->comps.data(), P->blocks.data(), P->fdesc.data(), P->fstate0.data(), P->list_tables.data(),
              P->list_huf.data(), P->list_seq.data(), P->list_k4f.data(), P->copies.data(), P->jframes.data(),
-             P->jblkd.data(), P->jsegd.data(), nullptr, nullptr};
+             P->jblkd.data(), P->jsegd.data(), nullptr, nullptr, nullptr};
+    P->frame_dict.assign(X.dset ? T.frames : 0, 0);
+    if (X.dset) S.frame_dict = P->frame_dict.data();
   }
   S.frame_out = P->frame_out.data();
   S.frame_cap = P->frame_cap.data();
@@ -615,18 +709,18 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
     PlanCounts c = cnt[k];
     for (const HostFrame& hf : hp.frames) plan_frame<true, JMax>(X, hf, hp.blocks.data(), c, S, &jm[k]);
   });
-  if (dict_comp) {
+  for (uint32_t k = 0; k < dict_comps; k++) {
     CompBlock pb{};
     pb.lit_type = LIT_COMPRESSED;
     pb.host_stage = PS_ALL;
     pb.nseq = 1;
     pb.modes[0] = pb.modes[1] = pb.modes[2] = M_FSE;
     pb.prebuilt = 1;
-    pb.huf_src = 0;
-    pb.tab_src[0] = pb.tab_src[1] = pb.tab_src[2] = 0;
-    pb.lut_slot = 0;
-    pb.fse_slot = 0;
-    S.comps[0] = pb;
+    pb.huf_src = (int32_t)k;
+    pb.tab_src[0] = pb.tab_src[1] = pb.tab_src[2] = (int32_t)k;
+    pb.lut_slot = k;
+    pb.fse_slot = k;
+    S.comps[k] = pb;
   }
   uint64_t j_maxseq = 0;
   for (const JMax& m : jm) j_maxseq = std::max(j_maxseq, m.m);
@@ -751,9 +845,16 @@ int upload_desc(zd_plan* P) {
         {W.jframes, P->jframes.data(), P->jframes.size() * sizeof(JFrame)},
         {W.jblkd, P->jblkd.data(), P->jblkd.size() * sizeof(JBlkDesc)},
         {W.jsegd, P->jsegd.data(), P->jsegd.size() * sizeof(JSegDesc)},
+        {W.frame_dict, P->frame_dict.data(), P->frame_dict.size() * 4},
     };
     for (const Piece& q : pieces)
       if (q.bytes) HIPCHK(hipMemcpy(P->d_ws + q.off, q.p, q.bytes, hipMemcpyHostToDevice));
+    if (P->dset) {
+      std::vector<const uint8_t*> dp;
+      for (const DictData* d : P->dset_used) dp.push_back(d->d_content);
+      dp.push_back(P->dset->d_none());
+      HIPCHK(hipMemcpy(P->d_ws + W.dict_ptrs, dp.data(), dp.size() * 8, hipMemcpyHostToDevice));
+    }
   }
   return 0;
 }
@@ -763,18 +864,31 @@ int upload_plan(zd_plan* P) {
   return upload_staging(P);
 }
 
-// A formatted dictionary's prebuilt comp 0, once per plan: its slots and its
-// state (zd_k_reset leaves comp 0's state alone, launch_reset keep_comps; no
-// launch writes the slots)
+// The prebuilt comps of the formatted dictionaries a plan uses (comp 0 of a
+// dictionary plan, comps 0..U-1 of a dictionary-set plan), once per plan:
+// their slots and their states (zd_k_reset leaves those states alone,
+// launch_reset keep_comps; no launch writes the slots)
 int upload_dict_tables(zd_plan* P) {
-  const DictData* dict = P->dict.get();
-  if (!dict || dict->raw) return 0;
-  CompState pcs{};
-  pcs.huf_bits = dict->huf_bits;
-  for (int k = 0; k < 3; k++) pcs.al[k] = dict->al[k];
-  if (hipMemcpy(P->d_ws + P->W.luts, dict->d_lut, LUT_ENTRIES * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
-      hipMemcpy(P->d_ws + P->W.fses, dict->d_fse, FSE_SLOT * 2, hipMemcpyDeviceToDevice) != hipSuccess ||
-      hipMemcpy(P->d_ws + P->W.comp_state, &pcs, sizeof pcs, hipMemcpyHostToDevice) != hipSuccess) {
+  if (!P->n_dict_comps) return 0;
+  std::vector<const DictData*> ds;
+  if (P->dict) ds.push_back(P->dict.get());
+  for (const DictData* d : P->dset_used)
+    if (!d->raw) ds.push_back(d);
+  std::vector<CompState> pcs(ds.size());
+  for (size_t u = 0; u < ds.size(); u++) {
+    pcs[u] = CompState{};
+    pcs[u].huf_bits = ds[u]->huf_bits;
+    for (int k = 0; k < 3; k++) pcs[u].al[k] = ds[u]->al[k];
+    if (hipMemcpy(P->d_ws + P->W.luts + u * (LUT_ENTRIES * 2), ds[u]->d_lut, LUT_ENTRIES * 2,
+                  hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipMemcpy(P->d_ws + P->W.fses + u * (FSE_SLOT * 2), ds[u]->d_fse, FSE_SLOT * 2, hipMemcpyDeviceToDevice) !=
+            hipSuccess) {
+      (void)hipGetLastError();
+      return ZD_E_HIP;
+    }
+  }
+  if (hipMemcpy(P->d_ws + P->W.comp_state, pcs.data(), pcs.size() * sizeof(CompState), hipMemcpyHostToDevice) !=
+      hipSuccess) {
     (void)hipGetLastError();
     return ZD_E_HIP;
   }
@@ -871,7 +985,7 @@ int plan_index(zd_plan* P, const uint8_t* src, size_t n) {
   static const char* wt = getenv("ZD_WALK_THREADS");   // experiments
   const unsigned hw = wt ? (unsigned)std::max(1, atoi(wt)) : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   const size_t T = n >= PAR_INDEX_MIN_BYTES ? std::min<size_t>(hw, n >> 20) : 1;
-  const bool rfc_empty_lits = P->dict != nullptr;   // (zd_walk.h parse_compressed)
+  const bool rfc_empty_lits = P->with_dict();   // (zd_walk.h parse_compressed)
   std::vector<HostPart> part(T);
   std::vector<int> st(T, 0);
   std::vector<size_t> end(T, 0), cut(T + 1);
@@ -1556,12 +1670,14 @@ extern "C" {
 // zd_plan_create / zd_plan_create_device: the walk (host or device), then
 // the descriptors, the workspace and the upload.
 static int plan_create(const uint8_t* src, const uint8_t* d_src, size_t n, uint32_t flags, hipStream_t s,
-                       zd_plan** out, uint64_t cap0, const std::shared_ptr<DictData>& dict = nullptr) {
+                       zd_plan** out, uint64_t cap0, const std::shared_ptr<DictData>& dict = nullptr,
+                       const std::shared_ptr<DictSetData>& dset = nullptr) {
   zd_plan* P = new (std::nothrow) zd_plan();
   if (!P) return ZD_E_NO_MEMORY;
   P->flags = flags;
   P->cap0 = cap0;
   P->dict = dict;
+  P->dset = dset;
   const auto t0 = std::chrono::steady_clock::now();
   if (d_src) {
     if (int r = plan_index_dev(P, d_src, n, s)) { zd_plan_destroy(P); return r; }
@@ -1581,6 +1697,7 @@ static int plan_create(const uint8_t* src, const uint8_t* d_src, size_t n, uint3
       return r;
     }
   } else if (!P->dev_built)
+    // (a dictionary set: every frame's dictionary from the plan's table, PlanCtx::dset)
     if (int r = build_plan(P, -1, none, 0, rep0, 0, true)) { zd_plan_destroy(P); return r; }
   P->info.src_bytes = n;
   const auto t1 = std::chrono::steady_clock::now();
@@ -1709,8 +1826,7 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
   // deep pool counters, K4J's round counters and done flags; ZD_RESET_COPIES
   // builds keep the six copy / fill launches it replaced)
 #ifndef ZD_RESET_COPIES
-  HIPCHK(launch_reset(P->d_ws, P->W, P->n_frames, P->n_comps, P->n_jframes != 0, P->j_pieces, s,
-                      (P->dict && !P->dict->raw) ? 1u : 0u));
+  HIPCHK(launch_reset(P->d_ws, P->W, P->n_frames, P->n_comps, P->n_jframes != 0, P->j_pieces, s, P->n_dict_comps));
 #else
   HIPCHK(hipMemcpyAsync(P->d_ws + P->W.frame_state, P->d_ws + P->W.frame_state0,
                         P->n_frames * sizeof(FrameState), hipMemcpyDeviceToDevice, s));
@@ -1756,6 +1872,7 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
   a.cus = (uint32_t)(k3_slots() / 64);
   a.stream = s;
   if (P->dict) a.dict = P->dict->d_content;
+  a.dict_set = P->dset != nullptr;
   // K3 as four lanes per block (K3Q, default): C3 (763 blocks) 2.89 -> 2.31
   // ms, a forked 8,192-block plan 4.24 -> 2.48, full C4 13.88 -> 13.80; the
   // plan flag ZD_F_SEQ_ONE_LANE keeps the one-lane chain (same records)
@@ -2015,9 +2132,15 @@ int zd::decode_resident(zd_plan* P, const uint8_t* src, size_t n, const uint8_t*
     if (cur->limit_stage == LS_CAPACITY) {
       // past K4J's 32 GiB, or with K4J forced off the streaming K4's int32
       // positions (plan_frame keys a larger frame out of domain): stop
-      // (a dictionary plan: the streaming K4's, less the content before the frame)
-      const uint64_t lim = cur->dict ? K4_MAX_FRAME_OUT - cur->dict->content
-                                     : k4j_mode_of(flags) == 0 ? K4_MAX_FRAME_OUT : K4J_MAX_FRAME_OUT;
+      // (a dictionary plan: the streaming K4's, less the content before the
+      // frame -- of the frame's own dictionary in a dictionary-set plan)
+      uint64_t lim = k4j_mode_of(flags) == 0 ? K4_MAX_FRAME_OUT : K4J_MAX_FRAME_OUT;
+      if (cur->dict) lim = K4_MAX_FRAME_OUT - cur->dict->content;
+      if (cur->dset) {
+        if (!cur->frames_ready()) { st = ZD_E_HIP; break; }
+        const int k = cur->dset->find(cur->frame(f).d);
+        lim = K4_MAX_FRAME_OUT - (k >= 0 ? cur->dset->d[(size_t)k]->content : 0);
+      }
       if (old_cap >= lim) break;
       cap0 = std::min<uint64_t>(lim, std::max<uint64_t>(4 * old_cap, old_cap + (1u << 20)));
     } else {
@@ -2027,7 +2150,7 @@ int zd::decode_resident(zd_plan* P, const uint8_t* src, size_t n, const uint8_t*
     if (!cur->frames_ready()) { st = ZD_E_HIP; break; }
     const size_t at = base + (size_t)cur->frame(f).d.src_offset;
     zd_plan* Q = nullptr;
-    const int r = plan_create(src + at, nullptr, n - at, flags, nullptr, &Q, cap0, cur->dict);
+    const int r = plan_create(src + at, nullptr, n - at, flags, nullptr, &Q, cap0, cur->dict, cur->dset);
     if (r) { st = r; break; }
     if (replans) (*replans)++;
     const uint64_t qob = std::max<uint64_t>(Q->info.out_bytes, 16);
@@ -2202,6 +2325,71 @@ int zd_decompress_dict(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, s
   return r;
 }
 
+// ---------------------------------------------------------------------------
+// Dictionary sets
+// ---------------------------------------------------------------------------
+int zd_dict_set_create(const zd_dict* const* dicts, size_t ndicts, int fallback, zd_dict_set** out) {
+  // ---- argument checks: no HIP call before they are done ----
+  if (!dicts || !out || !ndicts || ndicts > ZD_DICT_SET_MAX) return ZD_E_INVALID_ARG;
+  if (fallback < -1 || (fallback >= 0 && (size_t)fallback >= ndicts)) return ZD_E_INVALID_ARG;
+  for (size_t i = 0; i < ndicts; i++) {
+    if (!dicts[i] || !dicts[i]->p) return ZD_E_INVALID_ARG;
+    if (dicts[i]->p->dev != dicts[0]->p->dev) return ZD_E_INVALID_ARG;
+    // a raw-content dictionary (ID 0) that is not the fallback: no frame can name it
+    if (dicts[i]->p->id == 0 && (int)i != fallback) return ZD_E_INVALID_ARG;
+  }
+  std::vector<size_t> order(ndicts);
+  for (size_t i = 0; i < ndicts; i++) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    return dicts[a]->p->id != dicts[b]->p->id ? dicts[a]->p->id < dicts[b]->p->id : a < b;
+  });
+  for (size_t k = 1; k < ndicts; k++)
+    if (dicts[order[k]]->p->id == dicts[order[k - 1]]->p->id) return ZD_E_INVALID_ARG;   // (ID 0: at most the fallback)
+  std::shared_ptr<DictSetData> D(new (std::nothrow) DictSetData());
+  zd_dict_set* h = new (std::nothrow) zd_dict_set();
+  if (!D || !h) { delete h; return ZD_E_NO_MEMORY; }
+  std::unique_ptr<zd_dict_set> hold(h);
+  D->fallback_arg = fallback;
+  for (size_t k = 0; k < ndicts; k++) {
+    if ((int)order[k] == fallback) D->fallback = (int)k;
+    D->d.push_back(dicts[order[k]]->p);
+  }
+  HIPCHK(hipGetDevice(&D->dev));
+  if (D->dev != D->d[0]->dev) return ZD_E_INVALID_ARG;
+  HIPCHK(hipMalloc(&D->d_none_buf, 2 * DICT_PAD));
+  HIPCHK(hipMemset(D->d_none_buf, 0, 2 * DICT_PAD));
+  h->p = std::move(D);
+  *out = hold.release();
+  return ZD_OK;
+}
+
+void zd_dict_set_destroy(zd_dict_set* set) { delete set; }
+
+int zd_dict_set_info(const zd_dict_set* set, size_t* ndicts, int* fallback) {
+  if (!set || !set->p) return ZD_E_INVALID_ARG;
+  if (ndicts) *ndicts = set->p->d.size();
+  if (fallback) *fallback = set->p->fallback_arg;
+  return ZD_OK;
+}
+
+int zd_plan_create_dicts(const uint8_t* src, size_t n, uint32_t flags, const zd_dict_set* set, zd_plan** out) {
+  if (!out || (!src && n) || !set || !set->p) return ZD_E_INVALID_ARG;
+  int dev = -1;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev != set->p->dev) return ZD_E_INVALID_ARG;
+  return plan_create(src, nullptr, n, flags, nullptr, out, 0, nullptr, set->p);
+}
+
+int zd_decompress_dicts(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, uint32_t flags,
+                        const zd_dict_set* set) {
+  zd_plan* P = nullptr;
+  int r = zd_plan_create_dicts(src, n, flags, set, &P);
+  if (r) return r;
+  r = zd_plan_decompress(P, src, n, dst, cap, out_len);
+  zd_plan_destroy(P);
+  return r;
+}
+
 }  // extern "C"
 
 // ===========================================================================
@@ -2215,6 +2403,7 @@ struct zd_batch {
   size_t n = 0;
   uint32_t flags = 0;
   std::shared_ptr<DictData> dict;
+  std::shared_ptr<DictSetData> dset;     // zd_batch_create_dicts (never with `dict`)
   int dev = -1;
   uint8_t* d_gather = nullptr;           // the chunks' copies, 16-byte aligned, zero bytes between them
   uint64_t gather_alloc = 0;
@@ -2245,12 +2434,14 @@ void zd_batch_destroy(zd_batch* B) {
   delete B;
 }
 
-int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst, const uint64_t* dst_cap,
-                    size_t nchunks, uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out) {
+// zd_batch_create / zd_batch_create_dicts: one dictionary, a set, or neither
+static int batch_create(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
+                        const uint64_t* dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
+                        const zd_dict_set* set, void* stream, zd_batch** out) {
   // ---- argument checks: no HIP call before they are done ----
   if (!out || (flags & ZD_F_SKIPPABLE)) return ZD_E_INVALID_ARG;
   if (nchunks && (!d_src || !src_bytes || !d_dst || !dst_cap)) return ZD_E_INVALID_ARG;
-  if (nchunks >= (1ull << 31) || (dict && !dict->p)) return ZD_E_INVALID_ARG;
+  if (nchunks >= (1ull << 31) || (dict && !dict->p) || (set && !set->p)) return ZD_E_INVALID_ARG;
   const size_t n = nchunks;
   {
     std::vector<std::pair<uint64_t, uint64_t>> ranges;      // destinations of at least one byte
@@ -2278,6 +2469,10 @@ int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* c
   if (dict) {
     if (dict->p->dev != B->dev) return ZD_E_INVALID_ARG;
     B->dict = dict->p;
+  }
+  if (set) {
+    if (set->p->dev != B->dev) return ZD_E_INVALID_ARG;
+    B->dset = set->p;
   }
   const hipStream_t s = (hipStream_t)stream;
   const auto t0 = std::chrono::steady_clock::now();
@@ -2342,7 +2537,8 @@ int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* c
   B->P = P;
   P->flags = flags;
   P->dict = B->dict;
-  const bool rfc_empty_lits = P->dict != nullptr;
+  P->dset = B->dset;
+  const bool rfc_empty_lits = P->with_dict();
   std::vector<uint8_t> bind(n, 0);
   P->place_out.assign(head.begin() + 3 * (long)n, head.begin() + 4 * (long)n);
   P->place_cap = B->dst_cap;
@@ -2433,6 +2629,18 @@ int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* c
   return ZD_OK;
 }
 
+int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst, const uint64_t* dst_cap,
+                    size_t nchunks, uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out) {
+  return batch_create(d_src, src_bytes, d_dst, dst_cap, nchunks, flags, dict, nullptr, stream, out);
+}
+
+int zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
+                          const uint64_t* dst_cap, size_t nchunks, uint32_t flags, const zd_dict_set* set, void* stream,
+                          zd_batch** out) {
+  if (!set) return ZD_E_INVALID_ARG;
+  return batch_create(d_src, src_bytes, d_dst, dst_cap, nchunks, flags, nullptr, set, stream, out);
+}
+
 int zd_batch_info_get(const zd_batch* B, zd_batch_info* info) {
   if (!B || !info) return ZD_E_INVALID_ARG;
   *info = B->info;
@@ -2500,8 +2708,10 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
       }
       const uint32_t flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_J_ONE_ROUND)) | ZD_F_FRAME_SERIAL;
       zd_dict dh{B->dict};
+      zd_dict_set sh{B->dset};
       zd_batch* Q = nullptr;
-      int r = zd_batch_create(src.data(), sz.data(), dst.data(), dc.data(), m, flags, B->dict ? &dh : nullptr, s, &Q);
+      int r = batch_create(src.data(), sz.data(), dst.data(), dc.data(), m, flags, B->dict ? &dh : nullptr,
+                           B->dset ? &sh : nullptr, s, &Q);
       if (r) return r;
       std::vector<int32_t> st2(m);
       std::vector<uint64_t> ln2(m);

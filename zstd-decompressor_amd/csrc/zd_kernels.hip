@@ -2987,7 +2987,9 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
                                                    const uint16_t* __restrict__ fses, uint32_t f_begin,
                                                    uint32_t f_end, uint32_t f_step, const uint8_t* __restrict__ redo,
                                                    const K4Lds& M, const K4Fuse* fz, uint8_t* redo_out,
-                                                   const uint8_t* __restrict__ dict = nullptr) {
+                                                   const uint8_t* __restrict__ dict = nullptr,
+                                                   const uint8_t* const* __restrict__ dict_ptrs = nullptr,
+                                                   const uint32_t* __restrict__ frame_dict = nullptr) {
   static_assert(!DICT || (ZD_K4_OVS && !FZ), "the dictionary variant: pass 0's merged chunks, the streaming kernel");
   l_u8* const win = M.win;
   l_u8* const pat = M.pat;
@@ -3030,7 +3032,12 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
   // below K4_MAX_FRAME_OUT)
   const uint64_t cap64 = DICT ? F.out_cap + F.out_len0 : F.out_cap;
   if constexpr (DICT) {
-    X.dict = dict;
+    // (a dictionary-set plan: the frame's own dictionary, read beside its
+    // descriptor -- f is the wave's, so both loads are scalar and the pointer
+    // stays wave-uniform; a frame without a dictionary has lo = 0 and an
+    // address that is readable 16 bytes either side, which only the window
+    // preload below touches)
+    X.dict = dict_ptrs ? dict_ptrs[frame_dict[f]] : dict;
     X.lo = (int32_t)F.out_len0;
     X.out -= F.out_len0;
   }
@@ -3612,6 +3619,30 @@ __global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute_dict(const uint8_
   const K4Lds M{(l_u8*)win + K4_WPAD, (l_u8*)pat, (l_u8*)stab, (l_u8*)stg, (l_u32*)codelut};
   k4_body<false, true>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x,
                        f_end, gridDim.x, nullptr, M, nullptr, nullptr, dict);
+}
+
+// The streaming K4 of a dictionary-set plan (zd_plan_create_dicts): the same
+// body, each frame's dictionary from the plan's table -- dict_ptrs[frame_dict[f]]
+// is the content address of frame f's dictionary (F.out_len0 its size), or, for
+// a frame that decodes without one (F.out_len0 = 0), 16 zero bytes' middle.
+__global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute_dicts(const uint8_t* __restrict__ src, uint8_t* outbase,
+                                                   const FrameDesc* __restrict__ frames, FrameState* fstate,
+                                                   const BlockRec* __restrict__ blocks,
+                                                   const CompBlock* __restrict__ comp,
+                                                   const CompState* __restrict__ cstate,
+                                                   const uint8_t* __restrict__ lits,
+                                                   const uint64_t* __restrict__ seqs,
+                                                   const uint16_t* __restrict__ fses, uint32_t f_begin,
+                                                   uint32_t f_end, const uint8_t* const* __restrict__ dict_ptrs,
+                                                   const uint32_t* __restrict__ frame_dict) {
+  __shared__ __attribute__((aligned(16))) uint8_t win[K4_WPAD + K4_C];
+  __shared__ __attribute__((aligned(16))) uint8_t pat[64];
+  __shared__ __attribute__((aligned(16))) uint8_t stab[3 * FSE_TAB];
+  __shared__ __attribute__((aligned(16))) uint8_t stg[K4_STG + 16];
+  __shared__ uint32_t codelut[2 * 64];
+  const K4Lds M{(l_u8*)win + K4_WPAD, (l_u8*)pat, (l_u8*)stab, (l_u8*)stg, (l_u32*)codelut};
+  k4_body<false, true>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x,
+                       f_end, gridDim.x, nullptr, M, nullptr, nullptr, nullptr, dict_ptrs, frame_dict);
 }
 
 // ---------------------------------------------------------------------------
@@ -5841,7 +5872,12 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     if (n && k4_work) {  // frames on the streaming K4 (K4F's, K4J's and K0's exit at once)
       const bool tm = !redo && k4_work;
       if (tm) if ((e = dom(DOM_K4, 0)) != hipSuccess) return e;
-      if (a.dict)                              // a dictionary plan (never fused: no redo pass)
+      if (a.dict_set)                          // a dictionary-set plan: each frame's own dictionary
+        hipLaunchKernelGGL(zd_k_execute_dicts, dim3(n), dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp,
+                           (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
+                           (const uint16_t*)fses, f0, f1, (const uint8_t* const*)(ws + W.dict_ptrs),
+                           (const uint32_t*)(ws + W.frame_dict));
+      else if (a.dict)                         // a dictionary plan (never fused: no redo pass)
         hipLaunchKernelGGL(zd_k_execute_dict, dim3(n), dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp,
                            (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
                            (const uint16_t*)fses, f0, f1, a.dict);
@@ -5952,7 +5988,8 @@ namespace zd {
 // counters, K4J's round counters and done flags (six copy / fill launches
 // before, ~5 us each on the path of a few-frame plan).
 // cs_keep: the leading words of the block states that stay (a dictionary
-// plan's prebuilt comp 0, written once at plan creation; zd_k_reset_dict).
+// plan's prebuilt comp 0 -- a dictionary-set plan's prebuilt comps, one per
+// dictionary it uses -- written once at plan creation; zd_k_reset_dict).
 __device__ __attribute__((always_inline)) inline void reset_body(uint8_t* ws, const Workspace& W, uint64_t fs_words,
                                                                  uint64_t cs_words, uint32_t jp_words,
                                                                  uint64_t jdone_bytes, uint32_t cs_keep) {

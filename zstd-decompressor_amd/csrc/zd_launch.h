@@ -42,13 +42,17 @@ struct LaunchArgs {
   // device (frame positions [0, FrameDesc::out_len0)); the streaming K4 runs as
   // zd_k_execute_dict
   const uint8_t* dict = nullptr;
+  // a dictionary-set plan (zd_plan_create_dicts): the streaming K4 runs as
+  // zd_k_execute_dicts, each frame's dictionary from the workspace's table
+  // (Workspace::dict_ptrs, ::frame_dict)
+  bool dict_set = false;
 };
 
 // K1 table parse/build -> K2 Huffman literals -> K3 FSE sequences -> K4 execute.
 hipError_t launch_pipeline(const LaunchArgs& a);
 
 // zd_decode_async's state reset (frame / block states, K1 and K4J counters, K4J done flags).
-// keep_comps: the leading block states left as they are (a dictionary plan's prebuilt comp)
+// keep_comps: the leading block states left as they are (a dictionary plan's prebuilt comps)
 hipError_t launch_reset(uint8_t* ws, const Workspace& W, uint64_t n_frames, uint64_t n_comps, bool k4j,
                         uint64_t j_pieces, hipStream_t s, uint32_t keep_comps = 0);
 

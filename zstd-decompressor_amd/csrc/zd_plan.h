@@ -54,6 +54,16 @@ struct PlanCounts {
 constexpr int PLAN_FIELDS = 21;
 static_assert(sizeof(PlanCounts) == PLAN_FIELDS * 8, "PlanCounts: u64 fields only");
 
+// One dictionary of a dictionary-set plan (zd_plan_create_dicts), as the
+// per-frame pass needs it.  A plan's table holds the dictionaries that some
+// frame of the plan uses, sorted by ID (a raw-content dictionary, ID 0, first).
+struct PlanDict {
+  uint32_t dict_id;        // 0: raw content (only ever the fallback)
+  int32_t comp;            // the prebuilt comp carrying its tables, -1 for raw content
+  uint64_t content;        // content size
+  uint64_t rep[3];
+};
+
 // Plan-wide inputs of the per-frame pass.  `prev_*` seed the Treeless/Repeat
 // resolution (context API), -1 when absent.
 struct PlanCtx {
@@ -80,7 +90,28 @@ struct PlanCtx {
   // capacity is at most place_cap[fi].
   const uint64_t* place_out;
   const uint64_t* place_cap;
+  // Optional dictionary table (a dictionary-set plan, zd_plan_create_dicts /
+  // zd_batch_create_dicts; null everywhere else, the device planner included;
+  // `dict` is set with it): every frame takes out_len0, its first repeat
+  // offsets and its previous tables from the entry of its own Dictionary_ID
+  // instead of the plan-wide fields above.  A frame without an ID (or with ID
+  // 0) takes entry dset_fallback, or none at all when that is -1: it then
+  // decodes like a frame of a plan without a dictionary.  Frame fi's entry
+  // index goes to Sink::frame_dict (ndset: none).
+  const PlanDict* dset;
+  uint32_t ndset;
+  int32_t dset_fallback;
 };
+
+// The entry of Dictionary_ID id (non-zero) in a table sorted by ID, or -1.
+ZD_HD inline int32_t plan_dict_find(const PlanDict* t, uint32_t n, uint64_t id) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    if (t[m].dict_id < id) lo = m + 1; else hi = m;
+  }
+  return (lo < n && t[lo].dict_id == id) ? (int32_t)lo : -1;
+}
 
 // Where the filling pass writes: the plan's host vectors (small plans, the
 // context API) or the pinned upload staging at the workspace offsets.
@@ -95,6 +126,7 @@ struct Sink {
   JBlkDesc* jblkd;
   JSegDesc* jsegd;
   uint64_t *frame_out, *frame_cap;
+  uint32_t* frame_dict;    // a dictionary-set plan: the frame's entry in the plan's table (PlanCtx::dset), else null
 };
 
 // One frame's descriptors at the running indices c (build_plan).  FILL: the
@@ -112,19 +144,39 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   fs.key = hf.key;
   fs.rep[0] = X.rep0[0]; fs.rep[1] = X.rep0[1]; fs.rep[2] = X.rep0[2];
   fd.first_block = (uint32_t)c.blocks;
-  fd.out_len0 = X.out_len0;
+  uint64_t out_len0 = X.out_len0;
   int32_t huf_prev = X.prev_huf;
   int32_t tab_prev[3] = {X.prev_tab[0], X.prev_tab[1], X.prev_tab[2]};
   uint64_t bound = 0;
   bool seqs_in_frame = false;
-  // a frame that names another dictionary stops the plan like a frame that
-  // failed to index (no block of it is planned to run)
-  if (X.dict && hf.d.kind == ZD_FRAME_ZSTD && hf.d.dict_id != UINT64_MAX && hf.d.dict_id != 0 &&
-      hf.d.dict_id != X.dict_id)
+  const bool names_dict = hf.d.kind == ZD_FRAME_ZSTD && hf.d.dict_id != UINT64_MAX && hf.d.dict_id != 0;
+  if (X.dset) {
+    // the frame's own dictionary: by its ID, else the fallback, else none (a
+    // skippable frame: none, nothing of it reads one)
+    int32_t e = -1;
+    if (names_dict) e = plan_dict_find(X.dset, X.ndset, hf.d.dict_id);
+    else if (hf.d.kind == ZD_FRAME_ZSTD) e = X.dset_fallback;
+    if (names_dict && e < 0)
+      fs.key = plan_min(fs.key, make_key(PH_PARSE, 0, PS_STRUCT, 0, ZD_E_DICT_MISMATCH));
+    out_len0 = 0;
+    fs.rep[0] = 1; fs.rep[1] = 4; fs.rep[2] = 8;
+    huf_prev = tab_prev[0] = tab_prev[1] = tab_prev[2] = -1;
+    if (e >= 0) {
+      const PlanDict& d = X.dset[e];
+      out_len0 = d.content;
+      fs.rep[0] = d.rep[0]; fs.rep[1] = d.rep[1]; fs.rep[2] = d.rep[2];
+      huf_prev = tab_prev[0] = tab_prev[1] = tab_prev[2] = d.comp;
+    }
+    if (FILL) S.frame_dict[fi] = e >= 0 ? (uint32_t)e : X.ndset;
+  } else if (X.dict && names_dict && hf.d.dict_id != X.dict_id) {
+    // a frame that names another dictionary stops the plan like a frame that
+    // failed to index (no block of it is planned to run)
     fs.key = plan_min(fs.key, make_key(PH_PARSE, 0, PS_STRUCT, 0, ZD_E_DICT_MISMATCH));
+  }
+  fd.out_len0 = out_len0;
   const bool frame_failed_host = fs.key != KEY_NONE;
   // bytes of the frame's region before its first own byte (the context API's existing output)
-  const uint64_t own0 = X.dict ? 0 : X.out_len0;
+  const uint64_t own0 = X.dict ? 0 : out_len0;
   uint64_t jseg = 0;
   // a re-plan of a frame that overran (zd_plan_decompress): by identity, the
   // counting pass numbers each part's frames from 0
@@ -242,13 +294,13 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   fd.out_cap = cap;
   // K4J: frames of many compressed blocks, and any frame past the streaming
   // K4's int32 positions (distances, zd_common.h)
-  const bool to_j = X.out_len0 == 0 && !frame_failed_host && fd.nblocks && hf.ncomp && hf.d.kind == ZD_FRAME_ZSTD &&
+  const bool to_j = out_len0 == 0 && !frame_failed_host && fd.nblocks && hf.ncomp && hf.d.kind == ZD_FRAME_ZSTD &&
                     cap <= K4J_MAX_FRAME_OUT &&
                     (X.k4j_mode >= 0 ? X.k4j_mode == 1
                                      : ((X.k4j_auto && hf.ncomp >= X.k4j_min) || cap > K4_MAX_FRAME_OUT));
   // larger frames with sequences that K4J does not take (forced off, or past
   // its 32 GiB) are outside the GPU path's domain
-  if (!to_j && cap + (X.dict ? X.out_len0 : 0) > K4_MAX_FRAME_OUT && seqs_in_frame)
+  if (!to_j && cap + (X.dict ? out_len0 : 0) > K4_MAX_FRAME_OUT && seqs_in_frame)
     fs.key = plan_min(fs.key, make_key(PH_LIMIT, 0, 0, 0, ZD_E_OUT_OF_DOMAIN));
   if (to_j) {
     fd.lds = 2;
@@ -289,7 +341,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
     // executes the frames that fit it in plans of 256-768 frames, where the
     // streaming K4 runs one round at its batch latency (C3: 0.64 vs 0.75 ms);
     // it is slower on C4 (EXPERIMENTS.md).  ZD_K4F=1 / 0 forces it on / off.
-    fd.lds = (X.k4f_on && X.out_len0 == 0 && cap <= K4F_CAP_BYTES) ? 1u : 0u;
+    fd.lds = (X.k4f_on && out_len0 == 0 && cap <= K4F_CAP_BYTES) ? 1u : 0u;
   }
   if (fd.lds == 1) { if (FILL) S.list_k4f[c.k4f] = fi; c.k4f++; }
   // Leading raw / RLE blocks (skippable payloads too) have output offsets

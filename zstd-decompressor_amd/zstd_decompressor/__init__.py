@@ -16,8 +16,9 @@ from .parsing import ForwardByteParser
 from .frame import Frame, FrameIterator, Header, Skippable, ZStandard, MAX_WIN_SIZE
 from .block import Block
 from .decoding_context import DecodingContext
-from .batch import Batch, Dictionary, Plan, decode_tensors, decompress, frames_index
+from .batch import Batch, Dictionary, DictionarySet, Plan, decode_tensors, decompress, frames_index
 
 __all__ = ["ZdError", "ForwardByteParser", "Frame", "FrameIterator", "Header", "Skippable", "ZStandard",
-           "MAX_WIN_SIZE", "Block", "DecodingContext", "Batch", "Dictionary", "Plan", "decode_tensors", "decompress",
+           "MAX_WIN_SIZE", "Block", "DecodingContext", "Batch", "Dictionary", "DictionarySet",
+           "Plan", "decode_tensors", "decompress",
            "frames_index"]

@@ -1,6 +1,6 @@
 """Command line, mirroring the reference CLI (src/main.rs:7-60):
 
-    python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]
+    python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]...
 
 Decodes every frame of FILE on the GPU (the HIP pipeline behind zd_decompress)
 and writes the concatenated output to stdout or --output.  As in the
@@ -12,7 +12,9 @@ prints the parsed frames with `{:#x?}`).  Extra, beyond the reference:
 --check-checksums verifies Content_Checksum (XXH64) on the GPU and reports
 mismatches on stderr (the reference computes and never enforces it);
 -D DICT decodes every frame with the dictionary file DICT (formatted or raw
-content), as zstd's own -D does.
+content), as zstd's own -D does; -D given several times makes a dictionary
+set: every frame decodes with the dictionary its Dictionary_ID names, a frame
+without an ID with the one raw-content file if there is one, else the first.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ import argparse
 import sys
 
 from . import _lib
-from .batch import Dictionary, Plan, frames_index
+from .batch import Dictionary, DictionarySet, Plan, frames_index
 
 
 def _info(data: bytes) -> int:
@@ -44,7 +46,7 @@ def _info(data: bytes) -> int:
     return 0
 
 
-def main(argv=None) -> int:
+def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="zstd_decompressor", description="ZStandard decoder on MI355X (HIP)")
     ap.add_argument("filename", help="ZStandard file input, decompress it and output to stdout")
     ap.add_argument("-i", "--info", action="store_true", help="Dump information about frames instead of the output")
@@ -52,15 +54,30 @@ def main(argv=None) -> int:
     ap.add_argument("-p", "--print-skippable", action="store_true", help="Output Skippable frames as well")
     ap.add_argument("--check-checksums", action="store_true",
                     help="verify Content_Checksum (XXH64) on the GPU; mismatches go to stderr (not in the reference)")
-    ap.add_argument("-D", dest="dictionary", metavar="dict",
-                    help="decode with this dictionary file, as zstd -D (not in the reference)")
-    a = ap.parse_args(argv)
+    ap.add_argument("-D", dest="dictionary", metavar="dict", action="append",
+                    help="decode with this dictionary file, as zstd -D; repeat it for a set of dictionaries, "
+                         "each frame choosing by its Dictionary_ID (not in the reference)")
+    return ap
+
+
+def _dictionary(paths):
+    """One -D: that Dictionary, as ever.  Several: a DictionarySet whose
+    fallback is the one raw-content file, else the first."""
+    ds = [Dictionary(open(p, "rb").read()) for p in paths]
+    if len(ds) == 1:
+        return ds[0]
+    raw = [i for i, d in enumerate(ds) if d.raw_content]
+    return DictionarySet(ds, fallback=raw[0] if len(raw) == 1 else 0)
+
+
+def main(argv=None) -> int:
+    a = _parser().parse_args(argv)
     data = open(a.filename, "rb").read()
     if a.info:
         return _info(data)
     import torch
     try:
-        dictionary = Dictionary(open(a.dictionary, "rb").read()) if a.dictionary else None
+        dictionary = _dictionary(a.dictionary) if a.dictionary else None
     except _lib.ZdError as e:
         print(f"Error: dictionary: {e.name}", file=sys.stderr)
         return 1

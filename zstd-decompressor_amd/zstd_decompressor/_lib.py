@@ -91,6 +91,13 @@ SIGNATURES = {
                                C.POINTER(C.c_int)]),
     "zd_plan_create_dict": (C.c_int, [_vp, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
     "zd_decompress_dict": (C.c_int, [_vp, _sz, _vp, _sz, _szp, C.c_uint32, _vp]),
+    "zd_dict_set_create": (C.c_int, [C.POINTER(_vp), _sz, C.c_int, C.POINTER(_vp)]),
+    "zd_dict_set_destroy": (None, [_vp]),
+    "zd_dict_set_info": (C.c_int, [_vp, _szp, C.POINTER(C.c_int)]),
+    "zd_plan_create_dicts": (C.c_int, [_vp, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "zd_decompress_dicts": (C.c_int, [_vp, _sz, _vp, _sz, _szp, C.c_uint32, _vp]),
+    "zd_batch_create_dicts": (C.c_int, [C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64),
+                                        _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_create": (C.c_int, [C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64), _sz,
                                   C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_info_get": (C.c_int, [_vp, C.POINTER(BatchInfo)]),
@@ -225,6 +232,7 @@ RESERVED_BLOCK_TYPE = -50
 UNRECOGNIZED_MAGIC, FRAME_RESERVED_SET, MISSING_CHECKSUM, WINDOW_SIZE_TOO_BIG = -60, -61, -64, -66
 REF_PANIC, OUT_OF_DOMAIN, DST_TOO_SMALL, INVALID_ARG, HIP, NO_MEMORY, NOT_DECODED = -90, -91, -92, -93, -94, -95, -96
 DICT_CORRUPTED, DICT_MISMATCH = -98, -99
+DICT_SET_MAX = 4096    # ZD_DICT_SET_MAX
 F_SKIPPABLE = 1
 F_BLOCK_PARALLEL = 2   # every frame with a compressed block -> K4J (block-parallel execute)
 F_FRAME_SERIAL = 4     # no frame -> K4J

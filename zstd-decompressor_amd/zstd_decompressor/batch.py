@@ -78,6 +78,42 @@ class Dictionary:
             pass
 
 
+class DictionarySet:
+    """zd_dict_set: many dictionaries for one plan or batch, each frame
+    choosing its own by the Dictionary_ID in its header.  dictionaries: open
+    Dictionary objects with distinct IDs; fallback: index of the one for frames
+    without an ID (a raw-content dictionary can only be that one), or -1: such
+    frames decode with no dictionary.  Accepted wherever `dictionary=` is.  The
+    set keeps its dictionaries' device data alive, plans and batches keep the
+    set: close() in any order."""
+
+    def __init__(self, dictionaries, fallback: int = 0):
+        ds = list(dictionaries)
+        for d in ds:
+            if not isinstance(d, Dictionary):
+                raise TypeError("Dictionary objects required")
+        arr = (C.c_void_p * max(len(ds), 1))(*[d._h.value if d._h else None for d in ds])   # (a closed Dictionary: NULL, ZD_E_INVALID_ARG)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().zd_dict_set_create(arr, len(ds), fallback, C.byref(h)), "zd_dict_set_create")
+        self._h = h
+        self.dict_ids = tuple(d.dict_id for d in ds)
+        self.fallback = fallback
+
+    def __len__(self):
+        return len(self.dict_ids)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().zd_dict_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _decompress(data: bytes, flags: int, dictionary=None):
     """One plan (the host walk once) and zd_plan_decompress — what
     zd_decompress does, with the plan's output size read first."""
@@ -91,7 +127,7 @@ def _decompress(data: bytes, flags: int, dictionary=None):
 
 def decompress(data: bytes, print_skippable: bool = False, dictionary=None) -> bytes:
     """Decode every frame of `data` on the GPU (host in, host out);
-    dictionary: a Dictionary every frame decodes with."""
+    dictionary: a Dictionary every frame decodes with, or a DictionarySet."""
     st, out = _decompress(data, _lib.F_SKIPPABLE if print_skippable else 0, dictionary)
     _lib.check(st, "zd_decompress")
     return out
@@ -118,7 +154,7 @@ def decode_keyed(data: bytes, flags: int = 0):
 def decompress_status(data: bytes, print_skippable: bool = False, flags: int = 0, dictionary=None):
     """(status, output of the frames before the first failure).  flags: extra
     zd_plan flags (_lib.F_BLOCK_PARALLEL / F_FRAME_SERIAL pick the executor);
-    dictionary: a Dictionary every frame decodes with."""
+    dictionary: a Dictionary every frame decodes with, or a DictionarySet."""
     return _decompress(data, (_lib.F_SKIPPABLE if print_skippable else 0) | flags, dictionary)
 
 
@@ -135,8 +171,11 @@ class Plan:
             _lib.check(L.zd_plan_create(p, n, f, C.byref(h)), "zd_plan_create")
         else:
             if not getattr(dictionary, "_h", None):
-                raise ValueError("the Dictionary is closed")
-            _lib.check(L.zd_plan_create_dict(p, n, f, dictionary._h, C.byref(h)), "zd_plan_create_dict")
+                raise ValueError("the %s is closed" % type(dictionary).__name__)
+            if isinstance(dictionary, DictionarySet):
+                _lib.check(L.zd_plan_create_dicts(p, n, f, dictionary._h, C.byref(h)), "zd_plan_create_dicts")
+            else:
+                _lib.check(L.zd_plan_create_dict(p, n, f, dictionary._h, C.byref(h)), "zd_plan_create_dict")
         self._h = h
         self.info = PlanInfo()
         _lib.check(L.zd_plan_info_get(h, C.byref(self.info)), "zd_plan_info_get")
@@ -226,7 +265,8 @@ def _u64_array(values, n: int):
 
 class Batch:
     """zd_batch: N independently compressed chunks at N device addresses, each
-    decoded into its own device buffer with its own status.
+    decoded into its own device buffer with its own status (dictionary: a
+    Dictionary every chunk decodes with, or a DictionarySet).
 
     src_ptrs / dst_ptrs are device addresses (integers, e.g. tensor.data_ptr()),
     src_sizes / dst_caps byte counts.  A chunk holds one zstd frame (skippable
@@ -239,13 +279,19 @@ class Batch:
         if not (len(src_sizes) == len(dst_ptrs) == len(dst_caps) == n):
             raise ValueError("src_ptrs, src_sizes, dst_ptrs and dst_caps differ in length")
         if dictionary is not None and not getattr(dictionary, "_h", None):
-            raise ValueError("the Dictionary is closed")
+            raise ValueError("the %s is closed" % type(dictionary).__name__)
         sp, ss, dp, dc = (_u64_array(v, n) for v in (src_ptrs, src_sizes, dst_ptrs, dst_caps))
         vpp = C.POINTER(C.c_void_p)
         h = C.c_void_p()
-        _lib.check(_lib.lib().zd_batch_create(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, n, flags,
-                                              dictionary._h if dictionary else None, C.c_void_p(stream), C.byref(h)),
-                   "zd_batch_create")
+        if isinstance(dictionary, DictionarySet):
+            _lib.check(_lib.lib().zd_batch_create_dicts(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, n, flags,
+                                                        dictionary._h, C.c_void_p(stream), C.byref(h)),
+                       "zd_batch_create_dicts")
+        else:
+            _lib.check(_lib.lib().zd_batch_create(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, n, flags,
+                                                  dictionary._h if dictionary else None, C.c_void_p(stream),
+                                                  C.byref(h)),
+                       "zd_batch_create")
         self._h = h
         self.nchunks = n
         self.info = _lib.BatchInfo()
