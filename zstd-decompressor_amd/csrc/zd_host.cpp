@@ -161,6 +161,7 @@ struct zd_plan {
   uint8_t* d_ws = nullptr;
   uint64_t ws_bytes = 0;                 // size of the d_ws allocation (>= W.total: a cached block)
   int dev = -1;                          // the device d_ws and the aux stream belong to (upload_plan)
+  uint32_t cus = 256;                    // the CU count the plan was made for and is routed by (build_plan)
   uint64_t desc_bytes = 0;               // the host-filled head of the workspace (one upload)
   uint8_t* d_staging = nullptr;          // the output of a non-exact layout, or the copy an exact one is compacted from
   uint64_t staging_bytes = 0;
@@ -229,75 +230,9 @@ namespace {
 
 uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
-// Executor routing (zd_route, a pure function of the plan's shape and the
-// device's CU count; every bound below is in units of the CU count, measured
-// on the 256-CU MI355X):
-// * K4F takes one workgroup per CU: rounds of one frame per CU at ~0.21 ms
-//   each against the streaming K4's one round (~0.75 ms) of up to 16 frames
-//   per CU, so it pays for up to three rounds (scripts/exp_thresholds.sh:
-//   8192 frames 12.1 vs 7.7 ms per step): plans of 1-3 frames per CU.
-// * zd_k_fused holds four frames per workgroup and at most one workgroup per
-//   CU beside K2 (which its K4 waves wait for): plans of 1-4 single-block
-//   frames per CU (C3: 763 frames).
-// * K1's sequence half one wave per block (zd_k_tables_seqw) while the plan
-//   fits one round of 64 tables per CU (scripts/r3_k1wmax.sh: one rank's C4
-//   share at 8 GPUs, 10,240 blocks, +1 %; full C4, 81,920 blocks, -1 %).
-// * K2 beside K3 (the fork) where K3's last round of chains (64 per CU)
-//   leaves LDS for K2: the round's fill f = (blocks mod 64 CUs) / (64 CUs),
-//   measured with K3Q on C4-shaped plans (value, no fork -> fork): 10,240
-//   blocks (f 0.63) 194 -> 221 GB/s, 20,480 (0.25) 211 -> 234, 40,960 (0.5)
-//   247 -> 253; 12,288 (0.75) 221 -> 210, 16,384 (0) 251 -> 214, 32,768 (0)
-//   266 -> 250, 81,920 (0) 273 -> 268; 763 (C3) and 8,192 (0.5) fork.  So
-//   fork when 0 < f <= 0.65 (and at least one block per CU).
-// * Without the fork, K1's two halves on the two streams (C4 273.3 -> 274.0).
-// The ZD_FUSE / ZD_K4F / ZD_FORK / ZD_K1FORK / ZD_K1W_MAX environment
-// variables are experiment overrides read once per process (route_env);
-// nothing reads them unless they are set.
-struct RouteIn {
-  uint32_t cus;
-  uint64_t nframes, n_tables, n_seq, n_huf;
-  bool single_block_frames;      // every frame a zstd frame of one compressed block, no host-found error
-  bool context;                  // a DecodingContext plan (existing output or prebuilt tables)
-  uint32_t flags;                // ZD_F_*
-};
-struct Route {
-  bool fused = false, k4f = false, k1_seq_waves = false, fork = false, k1_fork = false, k3_lat = false;
-  bool k1_split = false;
-};
-constexpr uint32_t K4F_MIN_PER_CU = 1, K4F_MAX_PER_CU = 3;
-constexpr uint32_t FUSE_MIN_PER_CU = 1, FUSE_MAX_PER_CU = 4;
-constexpr uint32_t K1W_MAX_PER_CU = 64;
-constexpr uint32_t K3_CHAINS_PER_CU = 64;
-// K3L (one chain per wave, latency-first) while its waves fit two a SIMD:
-// beyond that K3Q's 16 chains a wave win on issue
-constexpr uint32_t K3L_MAX_PER_CU = 8;
-constexpr double FORK_MAX_FILL = 0.65;
-Route route_plan(const RouteIn& in) {
-  Route r;
-  const uint64_t cus = std::max<uint32_t>(in.cus, 1);
-  r.fused = !(in.flags & (ZD_F_NO_FUSE | ZD_F_SEQ_ONE_LANE | ZD_F_BLOCK_PARALLEL)) && !in.context &&
-            in.single_block_frames && in.nframes >= FUSE_MIN_PER_CU * cus && in.nframes <= FUSE_MAX_PER_CU * cus;
-  r.k4f = !r.fused && in.nframes >= K4F_MIN_PER_CU * cus && in.nframes <= K4F_MAX_PER_CU * cus;
-  r.k1_seq_waves = in.n_tables <= K1W_MAX_PER_CU * cus && !(in.flags & ZD_F_K1_LANES);
-  r.k1_split = (in.flags & ZD_F_K1_SPLIT) || (in.n_tables > K1W_MAX_PER_CU * cus && !(in.flags & ZD_F_K1_LANES));
-  const uint64_t slots = K3_CHAINS_PER_CU * cus, rem = in.n_seq % slots;
-  r.fork = in.n_seq >= cus && rem != 0 && (double)rem <= FORK_MAX_FILL * (double)slots;
-  r.k1_fork = !r.fork && in.n_huf && in.n_seq;
-  r.k3_lat = in.n_seq <= K3L_MAX_PER_CU * cus && !(in.flags & (ZD_F_SEQ_ONE_LANE | ZD_F_SEQ_NO_LATENCY));
-  return r;
-}
-// The environment overrides (experiments only), read once
-struct RouteEnv {
-  int fuse = -1, k4f = -1, fork = -1, k1fork = -1, k3l = -1;
-  int64_t k1w_max = -1;
-  RouteEnv() {
-    auto get = [](const char* n) { const char* e = getenv(n); return e ? atoi(e) : -1; };
-    fuse = get("ZD_FUSE"); k4f = get("ZD_K4F"); fork = get("ZD_FORK"); k1fork = get("ZD_K1FORK"); k3l = get("ZD_K3L");
-    if (const char* e = getenv("ZD_K1W_MAX")) k1w_max = atoll(e);
-  }
-};
+// The routing overrides (zd_route.h RouteEnv; experiments only), read once per process
 const RouteEnv& route_env() {
-  static const RouteEnv e;
+  static const RouteEnv e = RouteEnv::from_process();
   return e;
 }
 constexpr size_t PAR_INDEX_MIN_BYTES = 4u << 20;    // the host walk in parallel from 4 MiB of input (>= 512 frames)
@@ -395,31 +330,15 @@ HostStage& host_stage() {
 }
 constexpr uint64_t STAGE_MIN_BYTES = 1u << 20;     // smaller plans fill host vectors
 
-// K3's chains in flight on the current device: 64 per CU (LDS-bound)
-// (the CU count of each device, cached under a lock: plans are made and
-// launched from several threads)
-size_t k3_slots() {
-  static std::mutex m;
-  static std::vector<int> cus_of;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) { (void)hipGetLastError(); return 64 * 256; }
-  std::lock_guard<std::mutex> g(m);
-  if ((size_t)dev >= cus_of.size()) cus_of.resize((size_t)dev + 1, 0);
-  if (!cus_of[(size_t)dev]) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-    cus_of[(size_t)dev] = cus;
+// The current device's CU count, which a plan keeps and is routed by (zd_plan::cus)
+uint32_t device_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+    (void)hipGetLastError();
+    return 256;
   }
-  return 64 * (size_t)cus_of[(size_t)dev];
-}
-
-// K4J's mode from the plan flags (ZD_K4J=1 / 0, read once, forces it on / off)
-int k4j_mode_of(uint32_t flags) {
-  static const char* k4j_env = getenv("ZD_K4J");
-  return (flags & ZD_F_BLOCK_PARALLEL) ? 1 : (flags & ZD_F_FRAME_SERIAL) ? 0 : (k4j_env ? atoi(k4j_env) : -1);
+  return (uint32_t)cus;
 }
 
 // Every frame of the host walk a zstd frame of one compressed block, with no
@@ -461,26 +380,19 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   X.place_out = P->place_out.empty() ? nullptr : P->place_out.data();
   X.place_cap = P->place_out.empty() ? nullptr : P->place_cap.data();
   RouteIn in{};
-  in.cus = (uint32_t)(k3_slots() / 64);
+  in.cus = P->cus;
   in.nframes = P->nframes;
   // (a dictionary plan routes like a context plan: the streaming executor only)
   in.context = out_len0 != 0 || P->has_prebuilt || X.dict;
   in.flags = P->flags;
   in.single_block_frames = single;
-  const Route r = route_plan(in);
-  const RouteEnv& E = route_env();
+  const PlanRoute r = plan_route(in, X.dict, route_env());
   X.fused = r.fused;
-  // ZD_FUSE=1 forces the fused kernel on any plan of single-block frames
-  // (its K2 then runs before it, not beside it, zd_decode_async); 0 off
-  if (E.fuse == 0) X.fused = false;
-  if (E.fuse == 1) X.fused = !(P->flags & (ZD_F_NO_FUSE | ZD_F_SEQ_ONE_LANE | ZD_F_BLOCK_PARALLEL)) && !in.context &&
-                             single && P->nframes >= 1;
-  X.k4f_on = E.k4f >= 0 ? E.k4f == 1 : r.k4f;
-  if (X.fused) X.k4f_on = false;
-  X.k4j_mode = k4j_mode_of(P->flags);
+  X.k4f_on = r.k4f;
+  X.k4j_mode = k4j_mode_of(P->flags, route_env());
   X.k4j_min = P->nframes <= K4J_FEW_FRAMES ? K4J_MIN_BLOCKS_FEW : K4J_MIN_BLOCKS;
   X.k4j_auto = X.k4j_mode < 0 && out_len0 == 0 && j_candidates > 0 && j_candidates <= K4J_MAX_FRAMES;
-  if (X.dict) { X.k4f_on = false; X.k4j_auto = false; X.k4j_mode = 0; }
+  if (X.dict) { X.k4j_auto = false; X.k4j_mode = 0; }
   return X;
 }
 
@@ -546,7 +458,7 @@ void plan_totals(zd_plan* P, const PlanCounts& T, bool fused) {
   P->n_comps = T.comps; P->n_blocks = T.blocks; P->n_frames = T.frames;
   P->n_tables = T.tables; P->n_huf = T.huf; P->n_seq = T.seq; P->n_k4f = T.k4f; P->n_copies = T.copies;
   P->n_jframes = T.jframes; P->n_jblk = T.jblk; P->n_jseg = T.jseg; P->n_k0only = T.k0only;
-  P->fused = fused && T.jframes == 0 && T.k4f == 0;
+  P->fused = plan_fused(fused, T.jframes, T.k4f);
 }
 void plan_info(zd_plan* P, const PlanCounts& T) {
   zd_plan_info& I = P->info;
@@ -575,8 +487,9 @@ struct JMax {
 // context API keeps host vectors it edits afterwards.
 int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t out_len0,
                const uint64_t rep0[3], uint64_t fixed_cap, bool staged = false) {
+  P->cus = device_cus();
   uint64_t j_candidates = 0;
-  if (k4j_mode_of(P->flags) < 0 && out_len0 == 0) {
+  if (k4j_mode_of(P->flags, route_env()) < 0 && out_len0 == 0) {
     const uint32_t k4j_min = P->nframes <= K4J_FEW_FRAMES ? K4J_MIN_BLOCKS_FEW : K4J_MIN_BLOCKS;
     for (const HostPart& hp : P->parts)
       for (const HostFrame& hf : hp.frames) j_candidates += hf.key == KEY_NONE && hf.ncomp >= k4j_min;
@@ -1292,6 +1205,7 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s) {
   const HostFrame* d_frames = (const HostFrame*)B.d_out;
   const HostBlock* d_blocks = (const HostBlock*)(B.d_out + B.fb);
   P->nframes = F;
+  P->cus = device_cus();
   const uint32_t k4j_min = F <= K4J_FEW_FRAMES ? K4J_MIN_BLOCKS_FEW : K4J_MIN_BLOCKS;
   const uint64_t nt = (F + 255) / 256;
   if (!B.d_shape && hipMalloc(&B.d_shape, sizeof(PlanShape)) != hipSuccess) return ZD_E_HIP;
@@ -1306,7 +1220,7 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s) {
   memcpy(&shape, B.h_small, sizeof shape);
   const int32_t none[3] = {-1, -1, -1};
   const uint64_t rep0[3] = {1, 4, 8};
-  const PlanCtx X = plan_ctx(P, -1, none, 0, rep0, 0, shape.multi == 0, k4j_mode_of(P->flags) < 0 ? shape.jcand : 0);
+  const PlanCtx X = plan_ctx(P, -1, none, 0, rep0, 0, shape.multi == 0, k4j_mode_of(P->flags, route_env()) < 0 ? shape.jcand : 0);
   HIPCHK(launch_plan_count(X, d_frames, d_blocks, F, B.d_cnt, B.d_tot, B.d_shape, s));
   HIPCHK(hipMemcpyAsync(B.h_small, B.d_tot + nt * PLAN_FIELDS, PLAN_FIELDS * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(B.h_small + PLAN_FIELDS, B.d_shape, sizeof(PlanShape), hipMemcpyDeviceToHost, s));
@@ -1844,70 +1758,32 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
   a.out = out;
   a.ws = P->d_ws;
   a.W = P->W;
-  a.n_tables = (uint32_t)P->n_tables;
-  a.n_huf = (uint32_t)P->n_huf;
-  a.n_seq = (uint32_t)P->n_seq;
-  a.n_frames = (uint32_t)P->n_frames;
-  a.n_k4f = (uint32_t)P->n_k4f;
-  a.n_copies = (uint32_t)P->n_copies;
-  a.n_jframes = (uint32_t)P->n_jframes;
-  a.n_k0only = (uint32_t)P->n_k0only;
-  a.n_jblk = (uint32_t)P->n_jblk;
-  a.n_jseg = (uint32_t)P->n_jseg;
+  a.n_tables = (uint32_t)P->n_tables; a.n_huf = (uint32_t)P->n_huf; a.n_seq = (uint32_t)P->n_seq;
+  a.n_frames = (uint32_t)P->n_frames; a.n_k4f = (uint32_t)P->n_k4f; a.n_copies = (uint32_t)P->n_copies;
+  a.n_jframes = (uint32_t)P->n_jframes; a.n_k0only = (uint32_t)P->n_k0only;
+  a.n_jblk = (uint32_t)P->n_jblk; a.n_jseg = (uint32_t)P->n_jseg;
   // ZD_F_J_ONE_ROUND (a test switch, set per plan) cuts the rounds to one
   // of one hop: the path that re-plans a frame whose pointer jumping did not
   // converge, on the streaming executor
-  const bool one_round = (P->flags & ZD_F_J_ONE_ROUND) != 0;
-  a.j_rounds = one_round && P->j_rounds ? 1u : P->j_rounds;
+  a.j_rounds = (P->flags & ZD_F_J_ONE_ROUND) && P->j_rounds ? 1u : P->j_rounds;
   a.j_pieces = P->j_pieces;
-  // hops per pending word and K4J round (c3s, scripts/exp_jhops.sh, K4J ms
-  // with the word-per-lane rounds, round 5: 4 hops 1.91, 5 1.85, 6 1.75-1.77,
-  // 7 1.76, 8 1.78-1.79, 12 1.85, 16 1.90); ZD_J_HOPS overrides
-  static const char* hops_env = getenv("ZD_J_HOPS");
-  a.j_hops = one_round ? 1u : hops_env ? (uint32_t)std::max(1, atoi(hops_env)) : 6u;
-  // the sweeps after round 1 (c3s, round 6: 4 / 6 / 8 / 12 hops 3.19 /
-  // 3.09 / 3.08 / 3.06 ms a step, profiles/r6_graph_replay_ab.txt); ZD_J_HOPS2 overrides
-  static const char* hops2_env = getenv("ZD_J_HOPS2");
-  a.j_hops2 = one_round ? 1u : hops2_env ? (uint32_t)std::max(1, atoi(hops2_env)) : 12u;
-  a.cus = (uint32_t)(k3_slots() / 64);
+  a.cus = P->cus;
   a.stream = s;
+  // the route, resolved every launch (profiling may have been switched since
+  // the last one); the rest of `a` is what the route's launches need
+  const LaunchIn in{P->cus, P->n_frames, P->n_tables, P->n_huf, P->n_seq, P->flags, P->fused,
+                    P->dset ? K4_DICT_SET : P->dict ? K4_DICT : K4_PLAIN, P->profile ? 1 : P->profile_dom ? 2 : 0};
+  const LaunchRoute R = a.route = launch_route(in, route_env());
+  // (every plan has its second stream, aux_take, and a profiled one its events, zd_plan_set_profiling)
+  if (((R.fork || R.k1_fork) && !P->aux) || (R.profiling && !P->ev_made)) return ZD_E_HIP;
+  a.aux = P->aux; a.fork = P->fork; a.join = P->join;
+  a.events = P->ev; a.dom_events = P->dom_ev; a.dom_used = &P->dom_used;
+  P->dom_used = 0;
   if (P->dict) a.dict = P->dict->d_content;
-  a.dict_set = P->dset != nullptr;
-  // K3 as four lanes per block (K3Q, default): C3 (763 blocks) 2.89 -> 2.31
-  // ms, a forked 8,192-block plan 4.24 -> 2.48, full C4 13.88 -> 13.80; the
-  // plan flag ZD_F_SEQ_ONE_LANE keeps the one-lane chain (same records)
-  a.k3_quad = !(P->flags & ZD_F_SEQ_ONE_LANE);
-  a.events = P->profile ? P->ev : nullptr;
-  // routing (route_plan): K2 beside K3 on a second stream, K1's halves on
-  // the two streams, K1's sequence half one wave per block
-  RouteIn in{};
-  in.cus = (uint32_t)(k3_slots() / 64);
-  in.nframes = P->n_frames; in.n_tables = P->n_tables; in.n_seq = P->n_seq; in.n_huf = P->n_huf;
-  in.flags = P->flags;
-  const Route r = route_plan(in);
-  const RouteEnv& E = route_env();
-  // (a forced fused plan past FUSE_MAX_PER_CU frames per CU: K2 before it, its
-  // workgroups could not find room beside the fused ones)
-  const bool big_fused = P->fused && P->n_frames > FUSE_MAX_PER_CU * (uint64_t)in.cus;
-  const bool fork = E.fork >= 0 ? E.fork == 1 && !big_fused : r.fork && !big_fused;
-  if (fork) { a.aux = P->aux; a.fork = P->fork; a.join = P->join; }
-  if (!fork && !P->profile && (E.k1fork >= 0 ? E.k1fork == 1 && P->n_huf && P->n_seq : r.k1_fork)) {
-    a.aux = P->aux; a.fork = P->fork; a.join = P->join;
-    a.k1_fork = true;
-  }
-  a.k1_seq_waves = E.k1w_max >= 0 ? P->n_tables <= (uint64_t)E.k1w_max && !(P->flags & ZD_F_K1_LANES) : r.k1_seq_waves;
-  a.k1_split = r.k1_split;
-  a.k3_lat = E.k3l >= 0 ? E.k3l == 1 && !(P->flags & (ZD_F_SEQ_ONE_LANE | ZD_F_SEQ_NO_LATENCY)) : r.k3_lat;
-  P->last_fused = P->fused && !P->profile;
-  if (P->last_fused) {
-    a.fused = true;
+  P->last_fused = R.fused;
+  if (R.fused) {
     HIPCHK(hipMemsetAsync(P->d_ws + P->W.redo, 0, std::max<uint64_t>(P->n_frames, 1), s));
     HIPCHK(hipMemsetAsync(P->d_ws + P->W.k2done, 0, 4, s));
-  }
-  if (P->profile_dom) {
-    a.dom_events = P->dom_ev;
-    P->dom_used = 0;
-    a.dom_used = &P->dom_used;
   }
   HIPCHK(launch_pipeline(a));
   P->launched = true;
@@ -2134,7 +2010,7 @@ int zd::decode_resident(zd_plan* P, const uint8_t* src, size_t n, const uint8_t*
       // positions (plan_frame keys a larger frame out of domain): stop
       // (a dictionary plan: the streaming K4's, less the content before the
       // frame -- of the frame's own dictionary in a dictionary-set plan)
-      uint64_t lim = k4j_mode_of(flags) == 0 ? K4_MAX_FRAME_OUT : K4J_MAX_FRAME_OUT;
+      uint64_t lim = k4j_mode_of(flags, route_env()) == 0 ? K4_MAX_FRAME_OUT : K4J_MAX_FRAME_OUT;
       if (cur->dict) lim = K4_MAX_FRAME_OUT - cur->dict->content;
       if (cur->dset) {
         if (!cur->frames_ready()) { st = ZD_E_HIP; break; }
@@ -2903,6 +2779,7 @@ static int ctx_run(zd_context* c, zd_plan* P, const uint8_t* src, size_t n) {
   a.n_k4f = (uint32_t)P->list_k4f.size();
   a.n_copies = (uint32_t)P->copies.size();
   a.stream = s;
+  a.route = context_route();
   if (launch_pipeline(a) != hipSuccess) return ZD_E_HIP;
   // the frame state and every block's table state in one synchronisation
   const size_t nc = P->comps.size();
@@ -3160,6 +3037,7 @@ int zd_execute_sequences(zd_context* c, const uint32_t* ll, const uint32_t* ofv,
   a.n_k4f = (uint32_t)P.list_k4f.size();
   a.n_copies = (uint32_t)P.copies.size();
   a.stream = s;
+  a.route = context_route();
   FrameState st{};
   if (launch_pipeline(a) != hipSuccess ||
       hipMemcpyAsync(&st, P.d_ws + P.W.frame_state, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess ||

@@ -5749,30 +5749,32 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
   auto* luts = (uint16_t*)(ws + W.luts);
   auto* fses = (uint16_t*)(ws + W.fses);
   auto* seqs = (uint64_t*)(ws + W.seqs);
+  const LaunchRoute& R = a.route;
   hipStream_t s = a.stream;
   hipError_t e;
   // mode 2: events around launch group g on s
   auto dom = [&](int g, int end) -> hipError_t {
-    if (!a.dom_events) return hipSuccess;
+    if (R.profiling != 2) return hipSuccess;
     if (end) *a.dom_used |= 1u << g;
     return hipEventRecord(a.dom_events[2 * g + end], s);
   };
-  if (a.events) if ((e = hipEventRecord(a.events[0], s)) != hipSuccess) return e;
+  // mode 1: event k on s
+  auto ev = [&](int k) -> hipError_t { return R.profiling == 1 ? hipEventRecord(a.events[k], s) : hipSuccess; };
+  if ((e = ev(0)) != hipSuccess) return e;
   if (a.n_copies) {
     if ((e = dom(DOM_K0, 0)) != hipSuccess) return e;
     hipLaunchKernelGGL(zd_k_rawcopy, dim3(a.n_copies * K0_SPLIT), dim3(256), 0, s, a.src, a.out,
                        (const CopyDesc*)(ws + W.copies));
     if ((e = dom(DOM_K0, 1)) != hipSuccess) return e;
   }
-  if (a.events) if ((e = hipEventRecord(a.events[1], s)) != hipSuccess) return e;
+  if ((e = ev(1)) != hipSuccess) return e;
   // K2 and K3 are independent once their tables exist: with the fork, K1's
   // Huffman half and K2 run on the aux stream beside K1's sequence half and
-  // K3 (not when timing kernels one by one)
-  const bool fork = a.aux && !a.k1_fork && !a.events && a.n_huf && a.n_seq;
-  // without it, K1's two halves may still run on the two streams (joined
+  // K3; without it, K1's two halves may still run on the two streams (joined
   // before K2)
-  const bool k1f = a.aux && a.k1_fork && !a.events && a.n_tables;
-  hipStream_t s2 = fork ? a.aux : s;
+  const bool fork = R.fork, k1f = R.k1_fork;
+  hipStream_t s2 = fork ? a.aux : s;               // K2's stream
+  hipStream_t sh = fork || k1f ? a.aux : s;        // K1's Huffman half, where the halves are two launches
   if (fork || k1f) {
     if ((e = hipEventRecord(a.fork, s)) != hipSuccess) return e;
     if ((e = hipStreamWaitEvent(a.aux, a.fork, 0)) != hipSuccess) return e;
@@ -5812,33 +5814,27 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
   auto k1s_huf = [&](hipStream_t st) {
     k1s(zd_k_tables_parse<1>, zd_k_tables_build<1>, zd_k_tables<true, 1>, st, 1);
   };
-  const bool fz = a.fused && !a.events;
-  auto k1seqw = [&](hipStream_t st) {
-    hipLaunchKernelGGL(zd_k_tables_seqw, dim3(a.n_tables), dim3(64), 0, st, a.src, comp, cstate, fstate,
-                       (const uint32_t*)(ws + W.list_tables), a.n_tables, fses);
-  };
-  if (a.n_tables) {
-    if (fz) {                                  // the sequence half runs in zd_k_fused
-      if (a.k1_split) k1s_huf(s2);
-      else k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, s2, true);
-    } else if (a.k1_split) {                   // the same launch shapes as the lanes' below
-      if (fork || k1f) {
-        k1s_huf(k1f ? a.aux : s2);
-        k1s(zd_k_tables_parse<2>, zd_k_tables_build<2>, zd_k_tables<true, 2>, s, 2);
-      } else {
-        k1s(zd_k_tables_parse<3>, zd_k_tables_build<3>, zd_k_tables<true, 3>, s, 3);
-      }
-    } else if (a.k1_seq_waves) {               // few blocks: the sequence half one wave per block
-      k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, k1f ? a.aux : s2, true);
-      k1seqw(s);
-    } else if (fork || k1f) {
-      k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, k1f ? a.aux : s2, true);
+  const bool fz = R.fused;
+  if (a.n_tables) switch (R.k1) {
+    case K1_HUF_LANES: k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, s2, true); break;   // (the sequence half
+    case K1_HUF_SPLIT: k1s_huf(s2); break;                                                 // runs in zd_k_fused)
+    case K1_SPLIT_TWO:                         // the same launch shapes as the lanes' below
+      k1s_huf(sh);
+      k1s(zd_k_tables_parse<2>, zd_k_tables_build<2>, zd_k_tables<true, 2>, s, 2);
+      break;
+    case K1_SPLIT_BOTH: k1s(zd_k_tables_parse<3>, zd_k_tables_build<3>, zd_k_tables<true, 3>, s, 3); break;
+    case K1_LANES_SEQW:                        // few blocks: the sequence half one wave per block
+      k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, sh, true);
+      hipLaunchKernelGGL(zd_k_tables_seqw, dim3(a.n_tables), dim3(64), 0, s, a.src, comp, cstate, fstate,
+                         (const uint32_t*)(ws + W.list_tables), a.n_tables, fses);
+      break;
+    case K1_LANES_TWO:
+      k1(zd_k_tables<false, 1>, zd_k_tables<true, 1>, sh, true);
       k1(zd_k_tables<false, 2>, zd_k_tables<true, 2>, s, false);
-    } else {
-      k1(zd_k_tables<false, 3>, zd_k_tables<true, 3>, s, true);
-    }
+      break;
+    case K1_LANES_BOTH: k1(zd_k_tables<false, 3>, zd_k_tables<true, 3>, s, true); break;
   }
-  if (a.events) if ((e = hipEventRecord(a.events[2], s)) != hipSuccess) return e;
+  if ((e = ev(2)) != hipSuccess) return e;
   if (k1f) {
     if ((e = hipEventRecord(a.join, a.aux)) != hipSuccess) return e;
     if ((e = hipStreamWaitEvent(s, a.join, 0)) != hipSuccess) return e;
@@ -5846,22 +5842,25 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
   if (a.n_huf)
     hipLaunchKernelGGL(zd_k_huffman, dim3((a.n_huf + K2_BLOCKS - 1) / K2_BLOCKS), dim3(K2_LANES), 0, s2, a.src, comp,
                        cstate, fstate, (const uint32_t*)(ws + W.list_huf), a.n_huf, (const uint16_t*)luts, ws + W.lits,
-                       (a.fused && fork) ? (uint32_t*)(ws + W.k2done) : (uint32_t*)nullptr,
+                       (fz && fork) ? (uint32_t*)(ws + W.k2done) : (uint32_t*)nullptr,
                        (const uint8_t*)(ws + W.deep + 16));
   if (fork)
     if ((e = hipEventRecord(a.join, a.aux)) != hipSuccess) return e;
-  if (a.events) if ((e = hipEventRecord(a.events[3], s)) != hipSuccess) return e;
+  if ((e = ev(3)) != hipSuccess) return e;
   auto k3 = [&](const uint32_t* list, uint32_t n, hipStream_t st, const uint8_t* redo) {
-    if (n) {
-      if (a.k3_lat && a.k3_quad)
+    if (n) switch (R.k3) {
+      case K3_L:
         hipLaunchKernelGGL(zd_k_sequences_l, dim3(n), dim3(64), 0, st, a.src, comp, cstate, fstate, list, n,
                            (const uint16_t*)fses, seqs, redo);
-      else if (a.k3_quad)
+        break;
+      case K3_Q:
         hipLaunchKernelGGL(zd_k_sequences_q, dim3((n + K3Q_CHAINS - 1) / K3Q_CHAINS), dim3(64), 0, st, a.src, comp,
                            cstate, fstate, list, n, (const uint16_t*)fses, seqs, redo);
-      else
+        break;
+      case K3_ONE_LANE:
         hipLaunchKernelGGL(zd_k_sequences, dim3((n + K3_LANES - 1) / K3_LANES), dim3(K3_LANES), 0, st, a.src, comp,
                            cstate, fstate, list, n, (const uint16_t*)fses, seqs);
+        break;
     }
   };
   // the streaming K4 runs when some frame is not K4F's, K4J's or K0's alone
@@ -5872,19 +5871,19 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     if (n && k4_work) {  // frames on the streaming K4 (K4F's, K4J's and K0's exit at once)
       const bool tm = !redo && k4_work;
       if (tm) if ((e = dom(DOM_K4, 0)) != hipSuccess) return e;
-      if (a.dict_set)                          // a dictionary-set plan: each frame's own dictionary
+      if (R.k4 == K4_DICT_SET)                 // each frame's own dictionary
         hipLaunchKernelGGL(zd_k_execute_dicts, dim3(n), dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp,
                            (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
                            (const uint16_t*)fses, f0, f1, (const uint8_t* const*)(ws + W.dict_ptrs),
                            (const uint32_t*)(ws + W.frame_dict));
-      else if (a.dict)                         // a dictionary plan (never fused: no redo pass)
+      else if (R.k4 == K4_DICT)                // (never fused: no redo pass)
         hipLaunchKernelGGL(zd_k_execute_dict, dim3(n), dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp,
                            (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
                            (const uint16_t*)fses, f0, f1, a.dict);
       else
-      hipLaunchKernelGGL(zd_k_execute, dim3(n),
-                         dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp, (const CompState*)cstate,
-                         (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs, (const uint16_t*)fses, f0, f1, redo);
+        hipLaunchKernelGGL(zd_k_execute, dim3(n), dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp,
+                           (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
+                           (const uint16_t*)fses, f0, f1, redo);
       if (tm) if ((e = dom(DOM_K4, 1)) != hipSuccess) return e;
     }
     return hipSuccess;
@@ -5906,7 +5905,7 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     uint8_t* redo = ws + W.redo;
     const uint32_t k2need = fork ? (a.n_huf + K2_BLOCKS - 1) / K2_BLOCKS : 0;
     if ((e = dom(DOM_FUSED, 0)) != hipSuccess) return e;
-    if (a.k3_lat)
+    if (R.k3 == K3_L)
       hipLaunchKernelGGL(zd_k_fused<true>, dim3((a.n_frames + FZ_FRAMES - 1) / FZ_FRAMES), dim3(128 * FZ_FRAMES), 0, s,
                          a.src, a.out, frames, fstate, blocks, comp, cstate, (const uint8_t*)(ws + W.lits), seqs,
                          fses, a.n_frames, (const uint32_t*)(ws + W.k2done), k2need, redo);
@@ -5923,11 +5922,11 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     k3((const uint32_t*)(ws + W.list_seq), a.n_seq, s, nullptr);
     if (fork)
       if ((e = hipStreamWaitEvent(s, a.join, 0)) != hipSuccess) return e;
-    if (a.events) if ((e = hipEventRecord(a.events[4], s)) != hipSuccess) return e;
+    if ((e = ev(4)) != hipSuccess) return e;
     if ((e = k4(0, a.n_frames, s, nullptr)) != hipSuccess) return e;
     if ((e = k4f((const uint32_t*)(ws + W.list_k4f), a.n_k4f, s)) != hipSuccess) return e;
   }
-  if (a.events) if ((e = hipEventRecord(a.events[5], s)) != hipSuccess) return e;
+  if ((e = ev(5)) != hipSuccess) return e;
   if (a.n_jframes) {
     auto* jframes = (const JFrame*)(ws + W.jframes);
     auto* jd = (const JBlkDesc*)(ws + W.jblkd);
@@ -5954,11 +5953,11 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     const uint32_t nr = a.j_rounds < 2 ? a.j_rounds : 2u;
     for (uint32_t r = 1; r <= nr; r++)
       hipLaunchKernelGGL(zd_k_jround, gr, dim3(256), 0, s, a.out, frames, fstate, jframes, a.n_jframes,
-                         a.j_pieces, jst, pend, ws + W.jdone, r > 1 ? a.j_hops2 : a.j_hops, r, (uint32_t)(r == nr),
+                         a.j_pieces, jst, pend, ws + W.jdone, r > 1 ? R.j_hops2 : R.j_hops, r, (uint32_t)(r == nr),
                          r == nr ? a.j_rounds - nr + 1 : 1u);
     if ((e = dom(DOM_K4J, 1)) != hipSuccess) return e;
   }
-  if (a.events) if ((e = hipEventRecord(a.events[6], s)) != hipSuccess) return e;
+  if ((e = ev(6)) != hipSuccess) return e;
   return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 
 #include "zd_common.h"
 #include "zd_plan.h"
+#include "zd_route.h"
 
 namespace zd {
 
@@ -16,36 +17,26 @@ struct LaunchArgs {
   Workspace W;
   uint32_t n_tables, n_huf, n_seq, n_frames, n_k4f, n_copies;
   hipStream_t stream;
-  hipEvent_t* events;      // optional: N_KERNELS + 1 events recorded around the kernels
-  hipStream_t aux = nullptr;   // optional second stream: K2 beside K3
+  LaunchRoute route;       // what to launch and where (zd_route.h); the resources below only serve it
+  hipEvent_t* events = nullptr;   // route.profiling 1: N_KERNELS + 1 events recorded around the kernels
+  hipStream_t aux = nullptr;      // route.fork / route.k1_fork: the second stream and its two events
   hipEvent_t fork = nullptr, join = nullptr;
   uint32_t n_jframes = 0, n_jblk = 0, n_jseg = 0;   // K4J frames / their blocks / scatter segments
   uint32_t n_k0only = 0;                   // frames K0 copies whole (FrameDesc::lds 3)
   uint32_t j_rounds = 0;                   // K4J pointer-jumping rounds launched
   uint64_t j_pieces = 0;                   // 16-byte pieces over the K4J frames' regions
-  bool k3_lat = false;     // K3 as one block per wave (zd_k_sequences_l), few-block plans
-  bool k3_quad = true;     // K3 as four lanes per block (zd_k_sequences_q); false: one lane per block
-  uint32_t j_hops = 6;                     // K4J: hops per pending word and round (ZD_J_HOPS)
-  uint32_t j_hops2 = 12;                   // K4J: the same in the sweeps after round 1 (ZD_J_HOPS2)
   uint32_t cus = 256;                      // compute units of the device (K4J rounds' grid)
-  bool fused = false;                      // K3 + K4 as zd_k_fused, then the redo pass
-  bool k1_seq_waves = false;               // K1's sequence half one wave per block (zd_k_tables_seqw)
-  bool k1_split = false;                   // K1 as a parse pass and a build pass (zd_k_tables_parse / _build)
-  bool k1_fork = false;                    // no K2 | K3 fork: K1's halves on the two streams (aux, fork, join)
-  // optional (zd_plan_set_profiling mode 2): an event pair recorded on
-  // `stream` around each launch group that can carry a plan's work -- K0,
+  // route.profiling 2 (zd_plan_set_profiling mode 2): an event pair recorded
+  // on `stream` around each launch group that can carry a plan's work -- K0,
   // zd_k_fused, K4, K4F, the K4J kernels (kDomNames) -- with the fork and
   // fusion kept; bit g of *dom_used is set when group g launched
   hipEvent_t* dom_events = nullptr;
   uint32_t* dom_used = nullptr;
-  // a dictionary plan (zd_plan_create_dict): the dictionary's content on the
-  // device (frame positions [0, FrameDesc::out_len0)); the streaming K4 runs as
-  // zd_k_execute_dict
-  const uint8_t* dict = nullptr;
-  // a dictionary-set plan (zd_plan_create_dicts): the streaming K4 runs as
-  // zd_k_execute_dicts, each frame's dictionary from the workspace's table
+  // route.k4 == K4_DICT (zd_plan_create_dict): the dictionary's content on the
+  // device (frame positions [0, FrameDesc::out_len0)).  A dictionary-set plan
+  // (K4_DICT_SET) takes each frame's from the workspace's table
   // (Workspace::dict_ptrs, ::frame_dict)
-  bool dict_set = false;
+  const uint8_t* dict = nullptr;
 };
 
 // K1 table parse/build -> K2 Huffman literals -> K3 FSE sequences -> K4 execute.
