@@ -458,11 +458,19 @@ typedef struct zd_batch_info {
   uint64_t nsequences;
   uint64_t workspace_bytes; /* device memory the batch owns besides that copy */
   uint32_t executors;       /* ZD_EXEC_* bits, as zd_plan_info.executors */
-  uint32_t reserved;
+  uint32_t device_built;    /* 1: made by zd_batch_create_device(_dicts), else 0 */
   uint64_t gather_ns;       /* zd_batch_create: pointer-list upload + zd_k_gather */
   uint64_t walk_ns;         /*   zd_k_walk_chunks (count, fill) + the index's way back */
   uint64_t host_ns;         /*   descriptors (host work) */
   uint64_t upload_ns;       /*   workspace allocation + descriptor upload */
+  /* zd_batch_create_device, the same four phases (host wall clock):
+   *   gather_ns   the layout kernels (zd_k_batch_layout, the scans) + zd_k_gather,
+   *               to the wait after it
+   *   walk_ns     zd_k_walk_chunks count, the scan of the blocks' places and the
+   *               wait for their total; the fill pass and the capacity pass
+   *               (zd_k_batch_fit) are queued here and waited for in host_ns
+   *   host_ns     the device planner's launches (zd_k_plan_*) and their waits
+   *   upload_ns   workspace allocation, dictionary tables and small uploads */
 } zd_batch_info;
 
 /* A batch over nchunks chunks: chunk i is the src_bytes[i] bytes at device
@@ -509,6 +517,44 @@ int  zd_batch_create(const void* const* d_src, const uint64_t* src_bytes,
 int  zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes,
                            void* const* d_dst, const uint64_t* dst_cap, size_t nchunks,
                            uint32_t flags, const zd_dict_set* set, void* stream, zd_batch** out);
+/* zd_batch_create / zd_batch_create_dicts for a chunk table that is itself on
+ * the device: the four arrays are DEVICE arrays of nchunks entries, readable
+ * on `stream` when the call is made; they may be released when it returns (the
+ * batch keeps its own copies).  Layout, gather, header walk, capacity checks
+ * and descriptors are all built on the GPU: no per-block data and no frame /
+ * block index comes to the host, which reads back a few words per phase and
+ * 16 bytes a chunk.  The result is an ordinary batch (zd_batch_info.
+ * device_built = 1): every zd_batch_* call works on it with the meaning, the
+ * routing and the executors of the batch zd_batch_create makes from the same
+ * entries, and everything zd_batch_create says about a chunk holds.
+ * Synchronises `stream`.  What differs:
+ *  - ZD_E_INVALID_ARG for the whole call, before any HIP call: out NULL,
+ *    ZD_F_SKIPPABLE in flags, nchunks >= 2^31, a NULL array with nchunks > 0, a
+ *    destroyed dictionary or set.  (A dictionary or set of another device:
+ *    ZD_E_INVALID_ARG as in zd_batch_create.)  nchunks == 0 is ZD_OK without a
+ *    HIP call.
+ *  - The entries cannot be read without a round trip, so what zd_batch_create
+ *    refuses the whole batch for is a per-chunk outcome here: a NULL source
+ *    with a non-zero size, a NULL destination with a non-zero capacity, or an
+ *    address range that wraps makes that chunk ZD_E_INVALID_ARG (length 0);
+ *    nothing of it is read or written and no other chunk is touched.
+ *  - A chunk of 2^32 bytes or more is ZD_E_OUT_OF_DOMAIN, alone (the layout's
+ *    64-bit sums cannot wrap at any legal nchunks).
+ *  - Overlapping destinations are NOT checked (that needs a sort): keeping the
+ *    destination ranges disjoint is the caller's duty.  Overlapping ranges give
+ *    unspecified bytes in them; still no byte outside the union of the
+ *    destination ranges is written.
+ *  - ZD_E_OUT_OF_DOMAIN for the whole call when the chunks' 32 KiB pieces pass
+ *    zd_k_gather's grid (as zd_batch_create), known here once the layout's
+ *    totals are back. */
+int  zd_batch_create_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes,
+                            void* const* d_dst_ptrs, const uint64_t* d_dst_cap, size_t nchunks,
+                            uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out);
+/* zd_batch_create_device with a dictionary set (must not be NULL): the plan
+ * pays only for the dictionaries its own chunks use, as zd_batch_create_dicts. */
+int  zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes,
+                                  void* const* d_dst_ptrs, const uint64_t* d_dst_cap, size_t nchunks,
+                                  uint32_t flags, const zd_dict_set* set, void* stream, zd_batch** out);
 int  zd_batch_info_get(const zd_batch* batch, zd_batch_info* info);
 /* Launches the decode of every chunk on `stream`, ending with a kernel that
  * writes the batch's device result arrays (zd_batch_device_results).  No

@@ -8,7 +8,13 @@ Creation: the wall time of the call, and for the batch its split into gather /
 walk / host / upload (zd_batch_info); decode: each step between device events
 after warm-up.  Medians with min and max.  The unique source text is
 replicated to the workload's size (--unique-mib).  Writes one JSON line.
-usage: python scripts/time_batch.py [out.jsonl] [--steps N] [--creates N] [--unique-mib N] [--scale F]"""
+The device-creation leg (device_ab): the same four arrays uploaded once, then
+zd_batch_create (host arrays) and zd_batch_create_device (device arrays)
+alternating in this process, --creates times each: the wall time of each call
+and its zd_batch_info phase split, then the decode time of a batch of each
+kind.  --ab-out appends one line per workload with that leg alone.
+usage: python scripts/time_batch.py [out.jsonl] [--steps N] [--creates N] [--unique-mib N] [--scale F]
+                                    [--ab-out ab.jsonl]"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -32,6 +38,7 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--creates", type=int, default=5)
 ap.add_argument("--unique-mib", type=int, default=64)
 ap.add_argument("--scale", type=float, default=1.0, help="fraction of each workload's chunk count")
+ap.add_argument("--ab-out", help="append the device-creation leg of each workload here, one line each")
 args = ap.parse_args()
 WARMUP = 3
 dev = torch.device("cuda", 0)
@@ -124,6 +131,48 @@ def workload(name, chunk, nchunks, unique, compress, dictionary, dict_bytes):
     p_exec = p.info.executors
     p.close()
 
+    # ---- creation from device arrays against creation from host arrays ----
+    d_arrs = [torch.tensor(v, dtype=torch.int64, device=dev) for v in (src_ptrs, sizes, dst_ptrs, caps)]
+    torch.cuda.synchronize()
+
+    def make_device_batch():
+        return Batch.from_device(*d_arrs, dictionary=dictionary, stream=s.cuda_stream)
+    makers = {"host": make_batch, "device": make_device_batch}
+    for m in makers.values():
+        m().close()
+    ab = {k: {"wall": [], "gather": [], "walk": [], "host": [], "upload": []} for k in makers}
+    for _ in range(args.creates):
+        for k, m in makers.items():                      # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            x = m()
+            ab[k]["wall"].append((time.perf_counter() - t0) * 1e3)
+            for ph in ("gather", "walk", "host", "upload"):
+                ab[k][ph].append(getattr(x.info, ph + "_ns") / 1e6)
+            x.close()
+    device_ab = {}
+    for k, m in makers.items():
+        x = m()
+        d_dst.zero_()
+        ms = timed_steps(lambda: x.decode_async(s.cuda_stream), s)
+        st, ln = x.results(s.cuda_stream)
+        exact = not any(st) and sum(ln) == out_bytes and bool(torch.equal(d_dst[:out_bytes].cpu(), expect))
+        device_ab[k] = {"create_wall_ms": stats(ab[k]["wall"]),
+                        "create_ms": {ph: stats(ab[k][ph]) for ph in ("gather", "walk", "host", "upload")},
+                        "decode_ms": stats(ms), "bit_exact": exact, "executors": x.info.executors,
+                        "device_built": x.info.device_built, "nblocks": x.info.nblocks}
+        x.close()
+    device_ab["create_device_over_host"] = round(device_ab["device"]["create_wall_ms"]["median"] /
+                                                 device_ab["host"]["create_wall_ms"]["median"], 4)
+    device_ab["decode_device_over_host"] = round(device_ab["device"]["decode_ms"]["median"] /
+                                                 device_ab["host"]["decode_ms"]["median"], 4)
+    if args.ab_out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.ab_out)), exist_ok=True)
+        with open(args.ab_out, "a") as f:
+            f.write(json.dumps({"workload": name, "chunks": nchunks, "chunk_bytes": chunk,
+                                "dictionary_bytes": dict_bytes, "steps": args.steps, "warmup": WARMUP,
+                                "creates": args.creates, **device_ab}) + "\n")
+
     bmed, pmed = statistics.median(bms), statistics.median(pms)
     csum = sum(statistics.median(v) for v in split.values())
     return {
@@ -138,6 +187,7 @@ def workload(name, chunk, nchunks, unique, compress, dictionary, dict_bytes):
                  "create_wall_ms": stats(pwall), "decode_ms": stats(pms), "gbps": round(out_bytes / pmed / 1e6, 1),
                  "bit_exact": p_exact, "executors": p_exec},
         "decode_batch_over_plan": round(bmed / pmed, 4),
+        "device_ab": device_ab,
     }
 
 

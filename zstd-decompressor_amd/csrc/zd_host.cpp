@@ -480,6 +480,44 @@ struct JMax {
   void note(uint64_t n) { m = std::max(m, n); }
 };
 
+// The prebuilt comps at the head of a dictionary plan and, for a dictionary
+// set, the plan's table: the set's entries that some frame of the plan uses
+// (used[k] per entry of the set, in its order).
+void plan_dict_comps(zd_plan* P, const uint8_t* used) {
+  P->n_dict_comps = (P->dict && !P->dict->raw) ? 1u : 0u;
+  if (!P->dset) return;
+  const DictSetData& D = *P->dset;
+  P->dset_tab.clear();
+  P->dset_used.clear();
+  P->dset_fallback = -1;
+  for (size_t k = 0; k < D.d.size(); k++) {
+    if (!used[k]) continue;
+    const DictData& dd = *D.d[k];
+    PlanDict e{};
+    e.dict_id = dd.id;
+    e.comp = dd.raw ? -1 : (int32_t)P->n_dict_comps++;
+    e.content = dd.content;
+    for (int q = 0; q < 3; q++) e.rep[q] = dd.rep[q];
+    if ((int)k == D.fallback) P->dset_fallback = (int32_t)P->dset_tab.size();
+    P->dset_tab.push_back(e);
+    P->dset_used.push_back(&dd);
+  }
+}
+// Prebuilt comp k: the tables of the k-th formatted dictionary a plan uses (LUT slot k, FSE slot k)
+CompBlock prebuilt_comp(uint32_t k) {
+  CompBlock pb{};
+  pb.lit_type = LIT_COMPRESSED;
+  pb.host_stage = PS_ALL;
+  pb.nseq = 1;
+  pb.modes[0] = pb.modes[1] = pb.modes[2] = M_FSE;
+  pb.prebuilt = 1;
+  pb.huf_src = (int32_t)k;
+  pb.tab_src[0] = pb.tab_src[1] = pb.tab_src[2] = (int32_t)k;
+  pb.lut_slot = k;
+  pb.fse_slot = k;
+  return pb;
+}
+
 // Builds device-side descriptors from the host frames: one counting pass and
 // one filling pass over the parts in parallel (each part's entries start at
 // the counts of the parts before it), then the K4J descriptors in frame order.
@@ -498,30 +536,15 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
   // slot 0 and FSE slot 0, before every frame's (X.prev_huf / X.prev_tab name
   // it); a dictionary set: one such comp per formatted dictionary that a frame
   // of this plan uses, comps 0..U-1 with LUT and FSE slots 0..U-1
-  P->n_dict_comps = (P->dict && !P->dict->raw) ? 1u : 0u;
-  if (P->dset) {
-    const DictSetData& D = *P->dset;
-    std::vector<uint8_t> used(D.d.size(), 0);
-    for (const HostPart& hp : P->parts)
-      for (const HostFrame& hf : hp.frames) {
-        const int k = D.find(hf.d);
-        if (k >= 0) used[(size_t)k] = 1;
-      }
-    P->dset_tab.clear();
-    P->dset_used.clear();
-    P->dset_fallback = -1;
-    for (size_t k = 0; k < D.d.size(); k++) {
-      if (!used[k]) continue;
-      const DictData& dd = *D.d[k];
-      PlanDict e{};
-      e.dict_id = dd.id;
-      e.comp = dd.raw ? -1 : (int32_t)P->n_dict_comps++;
-      e.content = dd.content;
-      for (int q = 0; q < 3; q++) e.rep[q] = dd.rep[q];
-      if ((int)k == D.fallback) P->dset_fallback = (int32_t)P->dset_tab.size();
-      P->dset_tab.push_back(e);
-      P->dset_used.push_back(&dd);
-    }
+  {
+    std::vector<uint8_t> used(P->dset ? P->dset->d.size() : 0, 0);
+    if (P->dset)
+      for (const HostPart& hp : P->parts)
+        for (const HostFrame& hf : hp.frames) {
+          const int k = P->dset->find(hf.d);
+          if (k >= 0) used[(size_t)k] = 1;
+        }
+    plan_dict_comps(P, used.data());
   }
   const PlanCtx X = plan_ctx(P, prev_huf, prev_tab, out_len0, rep0, fixed_cap, host_single_block_frames(P),
                              j_candidates);
@@ -622,19 +645,7 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
     PlanCounts c = cnt[k];
     for (const HostFrame& hf : hp.frames) plan_frame<true, JMax>(X, hf, hp.blocks.data(), c, S, &jm[k]);
   });
-  for (uint32_t k = 0; k < dict_comps; k++) {
-    CompBlock pb{};
-    pb.lit_type = LIT_COMPRESSED;
-    pb.host_stage = PS_ALL;
-    pb.nseq = 1;
-    pb.modes[0] = pb.modes[1] = pb.modes[2] = M_FSE;
-    pb.prebuilt = 1;
-    pb.huf_src = (int32_t)k;
-    pb.tab_src[0] = pb.tab_src[1] = pb.tab_src[2] = (int32_t)k;
-    pb.lut_slot = k;
-    pb.fse_slot = k;
-    S.comps[k] = pb;
-  }
+  for (uint32_t k = 0; k < dict_comps; k++) S.comps[k] = prebuilt_comp(k);
   uint64_t j_maxseq = 0;
   for (const JMax& m : jm) j_maxseq = std::max(j_maxseq, m.m);
   carve_tail(P, W, T, o, T.jwords, T.jpieces, j_maxseq);
@@ -1201,7 +1212,18 @@ void parts_from(const std::vector<const HostFrame*>& kept, const HostBlock* bl, 
 // K4J frames included: plan_frame writes their descriptors at the scanned
 // K4J indices, and the count pass reports the largest K4J frame's sequence
 // count (the rounds), so no plan falls back to the host build.
-int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s) {
+// A batch (zd_batch_create_device) adds what DevPlanIn carries: the frames'
+// placement as device arrays, and the plan's dictionary or dictionary set
+// (P->dict / P->dset): the prebuilt comps at the plan's head, and for a set
+// the plan's table, built from the used flags that come back with the shape.
+struct DevPlanIn {
+  const uint64_t* place_out = nullptr;   // device arrays, one entry a frame (PlanCtx::place_out / place_cap)
+  const uint64_t* place_cap = nullptr;
+  const uint8_t* d_used = nullptr;       // a dictionary set: the used flag of each of its entries (device)
+  PlanDict* d_dset = nullptr;            //   and room for the plan's table on the device (one entry at least)
+  uint64_t alloc_ns = 0;                 // out: the workspace allocation and the small uploads
+};
+int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, DevPlanIn* in = nullptr) {
   const HostFrame* d_frames = (const HostFrame*)B.d_out;
   const HostBlock* d_blocks = (const HostBlock*)(B.d_out + B.fb);
   P->nframes = F;
@@ -1215,13 +1237,29 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s) {
     return ZD_E_HIP;
   HIPCHK(launch_plan_shape(d_frames, F, k4j_min, B.d_shape, s));
   HIPCHK(hipMemcpyAsync(B.h_small, B.d_shape, sizeof(PlanShape), hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> used(P->dset ? P->dset->d.size() : 0, 0);
+  if (P->dset && !used.empty()) {
+    if (!in || !in->d_used || !in->d_dset) return ZD_E_INVALID_ARG;
+    HIPCHK(hipMemcpyAsync(used.data(), in->d_used, used.size(), hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(hipStreamSynchronize(s));
   PlanShape shape;
   memcpy(&shape, B.h_small, sizeof shape);
-  const int32_t none[3] = {-1, -1, -1};
+  const int32_t none[3] = {-1, -1, -1}, pre[3] = {0, 0, 0};
   const uint64_t rep0[3] = {1, 4, 8};
-  const PlanCtx X = plan_ctx(P, -1, none, 0, rep0, 0, shape.multi == 0, k4j_mode_of(P->flags, route_env()) < 0 ? shape.jcand : 0);
-  HIPCHK(launch_plan_count(X, d_frames, d_blocks, F, B.d_cnt, B.d_tot, B.d_shape, s));
+  if (P->with_dict()) plan_dict_comps(P, used.data());
+  const DictData* D = P->dict.get();
+  const bool tabs = D && !D->raw;
+  PlanCtx X = plan_ctx(P, tabs ? 0 : -1, tabs ? pre : none, D ? D->content : 0, D ? D->rep : rep0, 0, shape.multi == 0,
+                       k4j_mode_of(P->flags, route_env()) < 0 ? shape.jcand : 0);
+  if (in) { X.place_out = in->place_out; X.place_cap = in->place_cap; }
+  if (P->dset) {
+    if (!in || !in->d_dset) return ZD_E_INVALID_ARG;
+    if (!P->dset_tab.empty())
+      HIPCHK(hipMemcpy(in->d_dset, P->dset_tab.data(), P->dset_tab.size() * sizeof(PlanDict), hipMemcpyHostToDevice));
+    X.dset = in->d_dset;
+  }
+  HIPCHK(launch_plan_count(X, d_frames, d_blocks, F, B.d_cnt, B.d_tot, B.d_shape, s, P->n_dict_comps));
   HIPCHK(hipMemcpyAsync(B.h_small, B.d_tot + nt * PLAN_FIELDS, PLAN_FIELDS * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(B.h_small + PLAN_FIELDS, B.d_shape, sizeof(PlanShape), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -1232,21 +1270,42 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s) {
   W = Workspace{};
   uint64_t o = 0;
   carve_head(W, T, o);
+  if (X.dset) {
+    W.frame_dict = o; o = align_up(o + 4 * std::max<uint64_t>(T.frames, 1), 256);
+    W.dict_ptrs = o; o = align_up(o + 8 * (uint64_t)(X.ndset + 1), 256);
+  }
   P->desc_bytes = o;
   plan_totals(P, T, X.fused);
   carve_tail(P, W, T, o, T.jwords, T.jpieces, shape.jmaxseq);
   W.hframes = o;
   o = align_up(o + sizeof(HostFrame) * std::max<uint64_t>(F, 1), 256);
   W.total = o;
+  const auto ta = std::chrono::steady_clock::now();
   HIPCHK(hipGetDevice(&P->dev));
   HIPCHK(ws_alloc(P->dev, W.total, &P->d_ws, &P->ws_bytes));
   uint8_t* b = P->d_ws;
+  // (the dictionaries' prebuilt comps 0..U-1 and a set's content addresses: the fill pass writes neither)
+  if (P->n_dict_comps) {
+    std::vector<CompBlock> pre_comps(P->n_dict_comps);
+    for (uint32_t k = 0; k < P->n_dict_comps; k++) pre_comps[k] = prebuilt_comp(k);
+    HIPCHK(hipMemcpy(b + W.comp, pre_comps.data(), pre_comps.size() * sizeof(CompBlock), hipMemcpyHostToDevice));
+  }
+  if (P->dset) {
+    std::vector<const uint8_t*> dp;
+    for (const DictData* d : P->dset_used) dp.push_back(d->d_content);
+    dp.push_back(P->dset->d_none());
+    HIPCHK(hipMemcpy(b + W.dict_ptrs, dp.data(), dp.size() * 8, hipMemcpyHostToDevice));
+  }
+  if (in)
+    in->alloc_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - ta)
+                       .count();
   uint64_t* d_fout = B.d_fo;
   uint64_t* d_fcap = B.d_fo + std::max<uint64_t>(F, 1);
   const Sink S{(CompBlock*)(b + W.comp), (BlockRec*)(b + W.blocks), (FrameDesc*)(b + W.frames),
                (FrameState*)(b + W.frame_state0), (uint32_t*)(b + W.list_tables), (uint32_t*)(b + W.list_huf),
                (uint32_t*)(b + W.list_seq), (uint32_t*)(b + W.list_k4f), (CopyDesc*)(b + W.copies),
-               (JFrame*)(b + W.jframes), (JBlkDesc*)(b + W.jblkd), (JSegDesc*)(b + W.jsegd), d_fout, d_fcap};
+               (JFrame*)(b + W.jframes), (JBlkDesc*)(b + W.jblkd), (JSegDesc*)(b + W.jsegd), d_fout, d_fcap,
+               X.dset ? (uint32_t*)(b + W.frame_dict) : nullptr};
   HIPCHK(launch_plan_fill(X, d_frames, d_blocks, F, B.d_cnt, B.d_tot, S, s));
   if (F) HIPCHK(hipMemcpyAsync(b + W.hframes, d_frames, F * sizeof(HostFrame), hipMemcpyDeviceToDevice, s));
   P->frame_out.resize(F);
@@ -2293,6 +2352,27 @@ struct zd_batch {
   uint32_t* d_nblk = nullptr;
   uint8_t* d_bind = nullptr;
   std::vector<uint64_t> goff, src_size, dst, dst_cap;
+  // a batch made from device arrays (zd_batch_create_device): the four vectors
+  // above stay empty until a call needs them (host_arrays), d_arr holds the
+  // chunks' capacities, first pieces and CHUNK_* flags too
+  bool device_built = false;
+  uint64_t *d_cap = nullptr, *d_piece0 = nullptr;
+  uint8_t* d_flag = nullptr;
+  int host_arrays() {
+    if (!device_built || goff.size() == n) return 0;
+    std::vector<uint64_t> o(n), z(n), d(n), c(n);
+    if (hipMemcpy(o.data(), d_off, 8 * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(z.data(), d_size, 8 * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(d.data(), d_out, 8 * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(c.data(), d_cap, 8 * n, hipMemcpyDeviceToHost) != hipSuccess) {
+      (void)hipGetLastError();
+      return ZD_E_HIP;
+    }
+    // (a chunk without a destination has capacity 0: any address serves)
+    for (size_t i = 0; i < n; i++) d[i] += (uint64_t)(uintptr_t)outbase;
+    goff = std::move(o); src_size = std::move(z); dst = std::move(d); dst_cap = std::move(c);
+    return 0;
+  }
   std::vector<int32_t> h_status;         // the last zd_batch_results
   std::vector<uint64_t> h_len;
   bool have_results = false;
@@ -2517,6 +2597,172 @@ int zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes, v
   return batch_create(d_src, src_bytes, d_dst, dst_cap, nchunks, flags, nullptr, set, stream, out);
 }
 
+// zd_batch_create_device / zd_batch_create_device_dicts: batch_create with the
+// four arrays on the device.  Layout, gather, walk, capacity pass and
+// descriptors all run there; the host reads back a few words a phase (the
+// layout's totals, the block count, the routing shape and a set's used flags,
+// the plan's totals) and the frames' output offsets and capacities.
+static int batch_create_device(const void* const* d_src, const uint64_t* d_src_bytes, void* const* d_dst,
+                               const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
+                               const zd_dict_set* set, void* stream, zd_batch** out) {
+  // ---- argument checks: no HIP call before they are done ----
+  if (!out || (flags & ZD_F_SKIPPABLE)) return ZD_E_INVALID_ARG;
+  if (nchunks && (!d_src || !d_src_bytes || !d_dst || !d_dst_cap)) return ZD_E_INVALID_ARG;
+  if (nchunks >= (1ull << 31) || (dict && !dict->p) || (set && !set->p)) return ZD_E_INVALID_ARG;
+  const size_t n = nchunks;
+  zd_batch* B = new (std::nothrow) zd_batch();
+  if (!B) return ZD_E_NO_MEMORY;
+  struct Drop { void operator()(zd_batch* b) const { zd_batch_destroy(b); } };
+  std::unique_ptr<zd_batch, Drop> hold(B);
+  B->n = n;
+  B->flags = flags;
+  B->device_built = true;
+  B->info.nchunks = n;
+  B->info.device_built = 1;
+  if (!n) { *out = hold.release(); return ZD_OK; }
+
+  HIPCHK(hipGetDevice(&B->dev));
+  if (dict) {
+    if (dict->p->dev != B->dev) return ZD_E_INVALID_ARG;
+    B->dict = dict->p;
+  }
+  if (set) {
+    if (set->p->dev != B->dev) return ZD_E_INVALID_ARG;
+    B->dset = set->p;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  auto ns = [](auto a, auto b) {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count();
+  };
+  const auto t0 = std::chrono::steady_clock::now();
+  // d_arr: src | size | off | piece0 | out | cap | boff | len | hash (u64), status | nblk (u32), bind | flag
+  // (u8), then the scans' scratch and the words that come back
+  const uint64_t nt = (n + 255) / 256;
+  const uint64_t scratch_words = 2 * (nt + 1) + 1, res_words = 4;
+  const uint64_t bytes_at = 9 * 8 * n + 2 * 4 * n, words_at = align_up(bytes_at + 2 * n, 8);
+  B->arr_bytes = words_at + 8 * (scratch_words + res_words);
+  HIPCHK(hipMalloc(&B->d_arr, B->arr_bytes));
+  uint64_t* a = (uint64_t*)B->d_arr;
+  B->d_src = a; B->d_size = a + n; B->d_off = a + 2 * n; B->d_piece0 = a + 3 * n; B->d_out = a + 4 * n;
+  B->d_cap = a + 5 * n; B->d_boff = a + 6 * n; B->d_len = a + 7 * n; B->d_hash = a + 8 * n;
+  B->d_status = (int32_t*)(a + 9 * n);
+  B->d_nblk = (uint32_t*)(B->d_status + n);
+  B->d_bind = B->d_arr + bytes_at;
+  B->d_flag = B->d_bind + n;
+  uint64_t* d_scratch = (uint64_t*)(B->d_arr + words_at);
+  uint64_t* d_res = d_scratch + scratch_words;
+  HIPCHK(hipMemsetAsync(B->d_arr, 0, B->arr_bytes, s));
+
+  DevWalkBufs& WB = dev_walk_bufs();
+  std::lock_guard<std::mutex> lk(WB.m);        // (its pinned words and device buffers, to the end of the call)
+  if (WB.dev != B->dev) {                      // buffers of another device: start over
+    if (WB.d_wr) (void)hipFree(WB.d_wr);
+    if (WB.d_out) (void)hipFree(WB.d_out);
+    WB.d_wr = nullptr; WB.cap_wr = 0; WB.d_out = nullptr; WB.cap_out = 0;
+    WB.dev = B->dev;
+  }
+  if (!WB.h_small && hipHostMalloc((void**)&WB.h_small, 64 * 8, hipHostMallocDefault) != hipSuccess) return ZD_E_HIP;
+
+  // ---- layout: the entries' checks, the gathered offsets, the pieces, the lowest destination ----
+  const BatchArrays A{B->d_src, B->d_size, B->d_off, B->d_piece0, B->d_out, B->d_cap, B->d_flag};
+  HIPCHK(launch_batch_layout((const uint64_t*)d_src, d_src_bytes, (const uint64_t*)d_dst, d_dst_cap, (uint32_t)n, A,
+                             d_scratch, d_res, s));
+  HIPCHK(hipMemcpyAsync(WB.h_small, d_res, 3 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint64_t total = WB.h_small[0], npieces = WB.h_small[1];
+  B->outbase = (uint8_t*)(uintptr_t)WB.h_small[2];
+  if (npieces * (COPY_PIECE / 4096) >= (1ull << 31)) return ZD_E_OUT_OF_DOMAIN;   // zd_k_gather's grid
+  HIPCHK(ws_alloc(B->dev, std::max<uint64_t>(total, 16), &B->d_gather, &B->gather_alloc));
+  const ChunkList L{B->d_src, B->d_size, B->d_off};
+  HIPCHK(launch_gather_scan(L, B->d_gather, B->d_piece0, (uint32_t)n, npieces, s));
+  HIPCHK(hipStreamSynchronize(s));             // (the sources may be released from here on; gather_ns ends here)
+  const auto t1 = std::chrono::steady_clock::now();
+
+  // ---- zd_k_walk_chunks: count, the blocks' places (a scan), fill; then the capacity pass ----
+  zd_plan* P = new (std::nothrow) zd_plan();
+  if (!P) return ZD_E_NO_MEMORY;
+  B->P = P;
+  P->flags = flags;
+  P->dict = B->dict;
+  P->dset = B->dset;
+  const bool rfc_empty_lits = P->with_dict();
+  HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, nullptr, nullptr, nullptr, false, s));
+  HIPCHK(launch_scan64(B->d_boff, B->d_nblk, n, 1, n, d_scratch, s));
+  HIPCHK(hipMemcpyAsync(WB.h_small, d_scratch + nt, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint64_t NB = WB.h_small[0];
+  if (NB >= (1ull << 32)) return ZD_E_OUT_OF_DOMAIN;
+  const size_t fb = align_up(n * sizeof(HostFrame), 256), bytes = fb + NB * sizeof(HostBlock);
+  if (!grow_dev(WB.d_out, WB.cap_out, bytes)) return ZD_E_HIP;
+  WB.fb = fb;
+  WB.bytes = bytes;
+  HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, B->d_boff, (HostFrame*)WB.d_out,
+                            (HostBlock*)(WB.d_out + fb), true, s));
+  // a dictionary set: its IDs go up, the used flags of its entries come back with the routing shape
+  struct Free { void operator()(void* p) const { if (p) (void)hipFree(p); } };
+  std::unique_ptr<void, Free> set_mem;
+  DevPlanIn in;
+  in.place_out = B->d_out;
+  in.place_cap = B->d_cap;
+  const uint32_t* d_ids = nullptr;
+  uint32_t nset = 0;
+  if (B->dset) {
+    const DictSetData& D = *B->dset;
+    nset = (uint32_t)D.d.size();
+    const uint64_t m = std::max<uint32_t>(nset, 1);
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, m * (sizeof(PlanDict) + 4 + 1)));      // table | IDs | used flags
+    set_mem.reset(p);
+    in.d_dset = (PlanDict*)p;
+    uint32_t* ids = (uint32_t*)(in.d_dset + m);
+    uint8_t* used = (uint8_t*)(ids + m);
+    std::vector<uint32_t> h_ids(m, 0);
+    for (uint32_t k = 0; k < nset; k++) h_ids[k] = D.d[k]->id;
+    HIPCHK(hipMemcpy(ids, h_ids.data(), 4 * m, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(used, 0, m, s));
+    d_ids = ids;
+    in.d_used = used;
+  }
+  HIPCHK(launch_batch_fit((HostFrame*)WB.d_out, (const HostBlock*)(WB.d_out + fb), B->d_cap, B->d_flag, (uint32_t)n,
+                          B->d_bind, d_ids, nset, B->dset ? B->dset->fallback : -1, (uint8_t*)in.d_used, s));
+  P->index_status = 0;
+  const auto t2 = std::chrono::steady_clock::now();
+
+  // ---- descriptors (zd_k_plan_*), placed at the chunks' destinations ----
+  if (int r = build_plan_device(P, WB, n, s, &in)) return r;
+  P->index_stop = P->nframes;
+  P->info.src_bytes = total;
+  const auto t3 = std::chrono::steady_clock::now();
+  if (int r = upload_dict_tables(P)) return r;
+  if (!aux_take(P)) return ZD_E_HIP;
+  const auto t4 = std::chrono::steady_clock::now();
+  zd_batch_info& I = B->info;
+  I.gathered_bytes = total;
+  I.nblocks = P->info.nblocks;
+  I.nsequences = P->info.nsequences;
+  I.workspace_bytes = P->W.total + B->arr_bytes;
+  I.executors = P->info.executors;
+  I.gather_ns = ns(t0, t1);
+  I.walk_ns = ns(t1, t2);
+  I.host_ns = ns(t2, t3) - std::min(in.alloc_ns, ns(t2, t3));
+  I.upload_ns = ns(t3, t4) + in.alloc_ns;
+  *out = hold.release();
+  return ZD_OK;
+}
+
+int zd_batch_create_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
+                           const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict, void* stream,
+                           zd_batch** out) {
+  return batch_create_device(d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, nchunks, flags, dict, nullptr, stream, out);
+}
+
+int zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
+                                 const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict_set* set,
+                                 void* stream, zd_batch** out) {
+  if (!set) return ZD_E_INVALID_ARG;
+  return batch_create_device(d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, nchunks, flags, nullptr, set, stream, out);
+}
+
 int zd_batch_info_get(const zd_batch* B, zd_batch_info* info) {
   if (!B || !info) return ZD_E_INVALID_ARG;
   *info = B->info;
@@ -2571,6 +2817,7 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
         redo.push_back(i);
     }
     if (!redo.empty()) {
+      if (int r = B->host_arrays()) return r;
       const size_t m = redo.size();
       std::vector<const void*> src(m);
       std::vector<void*> dst(m);
@@ -2623,6 +2870,7 @@ int zd_batch_checksums(zd_batch* B, void* stream, int32_t* ok, uint64_t* hash) {
   if (!B->have_results)
     if (int r = zd_batch_results(B, stream, nullptr, nullptr, 0, nullptr)) return r;
   const size_t n = B->n;
+  if (!B->P->frames_ready()) return ZD_E_HIP;   // (a device-built batch's frame index comes back here, once)
   std::vector<uint64_t> h(n);
   HIPCHK(launch_xxh64(B->outbase, B->d_out, B->d_len, (uint32_t)n, B->d_hash, s));
   HIPCHK(hipStreamSynchronize(s));

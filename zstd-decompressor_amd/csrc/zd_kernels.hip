@@ -19,6 +19,7 @@
 //                      value decode of decoders/sequence.rs:41-55); K4F / K4J /
 //                      zd_k_fused: the executors for other plan shapes
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 
@@ -6235,7 +6236,10 @@ __global__ __launch_bounds__(256) void zd_k_plan_count(PlanCtx X, const HostFram
   PlanCounts c{};
   const Sink none{};
   DevJMax jm{(unsigned long long*)&shape->jmaxseq};
+  // (a batch's placement is by plan frame index: counted from the frame's own, taken off again)
+  if (X.place_out) c.frames = f;
   plan_frame<false, DevJMax>(X, frames[f], blocks, c, none, &jm);
+  if (X.place_out) c.frames -= f;
   cnt[f] = c;
 }
 // Exclusive scan of the PlanCounts words over frames, in place: tile t's
@@ -6260,10 +6264,14 @@ __global__ __launch_bounds__(256) void zd_k_plan_scan_tiles(uint64_t* cnt, uint6
     __syncthreads();
   }
 }
-__global__ __launch_bounds__(64) void zd_k_plan_scan_sums(uint64_t* tot, uint64_t ntiles) {
+// dict_comps: the prebuilt comps at the plan's head (a dictionary batch): the
+// comps and their LUT and FSE slots start after them, as build_plan's do.
+__global__ __launch_bounds__(64) void zd_k_plan_scan_sums(uint64_t* tot, uint64_t ntiles, uint64_t dict_comps) {
   const int w = threadIdx.x;
   if (w >= PLAN_FIELDS) return;
-  uint64_t acc = 0;
+  constexpr int W_COMPS = offsetof(PlanCounts, comps) / 8, W_LUTS = offsetof(PlanCounts, luts) / 8,
+                W_FSES = offsetof(PlanCounts, fses) / 8;
+  uint64_t acc = (w == W_COMPS || w == W_LUTS || w == W_FSES) ? dict_comps : 0;
   for (uint64_t t = 0; t < ntiles; t++) {
     const uint64_t v = tot[t * PLAN_FIELDS + w];
     tot[t * PLAN_FIELDS + w] = acc;
@@ -6290,13 +6298,13 @@ hipError_t launch_plan_shape(const HostFrame* frames, uint64_t nf, uint32_t k4j_
   return hipGetLastError();
 }
 hipError_t launch_plan_count(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
-                             uint64_t* cnt, uint64_t* tot, PlanShape* shape, hipStream_t s) {
+                             uint64_t* cnt, uint64_t* tot, PlanShape* shape, hipStream_t s, uint32_t dict_comps) {
   const uint32_t nt = (uint32_t)((nf + 255) / 256);
   if (nf) {
     hipLaunchKernelGGL(zd_k_plan_count, dim3(nt), dim3(256), 0, s, X, frames, blocks, nf, (PlanCounts*)cnt, shape);
     hipLaunchKernelGGL(zd_k_plan_scan_tiles, dim3(nt), dim3(256), 0, s, cnt, nf, tot);
   }
-  hipLaunchKernelGGL(zd_k_plan_scan_sums, dim3(1), dim3(64), 0, s, tot, (uint64_t)nt);
+  hipLaunchKernelGGL(zd_k_plan_scan_sums, dim3(1), dim3(64), 0, s, tot, (uint64_t)nt, (uint64_t)dict_comps);
   return hipGetLastError();
 }
 hipError_t launch_plan_fill(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
@@ -6330,14 +6338,12 @@ hipError_t launch_walk(const uint8_t* src, uint64_t n, uint64_t first, uint64_t 
 // for a chunk's last piece also zeroes the bytes up to the next chunk's copy.
 // Nothing outside [src, src + size) is read.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void zd_k_gather(ChunkList L, uint8_t* gathered,
-                                                   const GatherPiece* __restrict__ pieces) {
-  const uint32_t sub = blockIdx.x % K0_SPLIT;
-  const GatherPiece p = pieces[blockIdx.x / K0_SPLIT];
-  const uint64_t size = L.size[p.chunk], at = (uint64_t)p.piece * COPY_PIECE;
-  const uint32_t n = (uint32_t)min((uint64_t)COPY_PIECE, size - at);     // (at <= size: the host's piece list)
-  const uint8_t* s = (const uint8_t*)(uintptr_t)L.src[p.chunk] + at;
-  uint8_t* d = gathered + L.off[p.chunk] + at;
+// (one workgroup's share of piece `piece` of chunk `chunk`)
+__device__ inline void gather_piece(const ChunkList& L, uint8_t* gathered, uint32_t chunk, uint32_t piece, uint32_t sub) {
+  const uint64_t size = L.size[chunk], at = (uint64_t)piece * COPY_PIECE;
+  const uint32_t n = (uint32_t)min((uint64_t)COPY_PIECE, size - at);     // (at <= size: the piece list)
+  const uint8_t* s = (const uint8_t*)(uintptr_t)L.src[chunk] + at;
+  uint8_t* d = gathered + L.off[chunk] + at;
   const int t = threadIdx.x;
   const uint32_t x = 16 * (256 * sub + (uint32_t)t);
   if (x + 16 <= n) *(g_u32x4*)(d + x) = ldg16(s + x);
@@ -6350,6 +6356,26 @@ __global__ __launch_bounds__(256) void zd_k_gather(ChunkList L, uint8_t* gathere
       if ((uint32_t)t < pad) d[n + t] = 0;
     }
   }
+}
+__global__ __launch_bounds__(256) void zd_k_gather(ChunkList L, uint8_t* gathered,
+                                                   const GatherPiece* __restrict__ pieces) {
+  const GatherPiece p = pieces[blockIdx.x / K0_SPLIT];
+  gather_piece(L, gathered, p.chunk, p.piece, blockIdx.x % K0_SPLIT);
+}
+// zd_k_gather without a piece list (zd_batch_create_device): piece q of the
+// batch belongs to the last chunk whose first piece (piece0, the exclusive
+// scan of the chunks' piece counts, every count >= 1) is at or below q.
+__global__ __launch_bounds__(256) void zd_k_gather_scan(ChunkList L, uint8_t* gathered,
+                                                        const uint64_t* __restrict__ piece0, uint32_t n,
+                                                        uint64_t npieces) {
+  const uint64_t q = blockIdx.x / K0_SPLIT;
+  if (q >= npieces || !n) return;
+  uint32_t lo = 0, hi = n;            // piece0[lo] <= q < piece0[hi] (piece0[n] = npieces)
+  while (hi - lo > 1) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    if (piece0[m] <= q) lo = m; else hi = m;
+  }
+  gather_piece(L, gathered, lo, (uint32_t)(q - piece0[lo]), blockIdx.x % K0_SPLIT);
 }
 
 hipError_t launch_gather(const ChunkList& L, uint8_t* gathered, const GatherPiece* d_pieces, uint64_t npieces,
@@ -6418,6 +6444,207 @@ hipError_t launch_batch_results(const FrameState* fstate, const uint8_t* bind, u
                                 uint64_t* len, hipStream_t s) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(zd_k_batch_results, dim3((n + 255) / 256), dim3(256), 0, s, fstate, bind, n, status, len);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Batches made from device arrays (zd_batch_create_device): what
+// zd_batch_create computes on the host from its four host arrays -- the checks
+// on each entry, the gathered layout, the pieces, the lowest destination, the
+// blocks' places, the capacity checks -- computed here, one lane per chunk.
+// ---------------------------------------------------------------------------
+
+// zd_k_batch_layout: chunk i's entry checked and copied into the batch's own
+// arrays.  A NULL address with a non-zero count or a range that wraps
+// (CHUNK_INVALID), or a chunk of 2^32 bytes or more (CHUNK_TOO_LARGE), becomes
+// a chunk of no bytes and no destination: nothing of it is read or written.
+// A.off / A.piece0 get the chunk's gathered bytes and pieces (scanned next),
+// A.out its destination address (zd_k_batch_place turns it into an offset);
+// *lowest (UINT64_MAX before) the lowest non-NULL destination.
+__global__ __launch_bounds__(256) void zd_k_batch_layout(const uint64_t* __restrict__ src,
+                                                         const uint64_t* __restrict__ size,
+                                                         const uint64_t* __restrict__ dst,
+                                                         const uint64_t* __restrict__ cap, uint32_t n, BatchArrays A,
+                                                         unsigned long long* lowest) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long low = ~0ull;
+  if (i < n) {
+    uint64_t s = src[i], z = size[i], d = dst[i], c = cap[i];
+    uint8_t flag = CHUNK_OK;
+    if ((!s && z) || (!d && c) || s + z < s || d + c < d) flag = CHUNK_INVALID;
+    else if (z >= (1ull << 32)) flag = CHUNK_TOO_LARGE;
+    if (flag) s = z = d = c = 0;
+    A.src[i] = s;
+    A.size[i] = z;
+    A.off[i] = ((z + 15) & ~15ull) + ZD_SRC_PADDING;
+    const uint64_t np = (z + COPY_PIECE - 1) / COPY_PIECE;
+    A.piece0[i] = np ? np : 1;
+    A.out[i] = d;
+    A.cap[i] = c;
+    A.flag[i] = flag;
+    if (d) low = d;
+  }
+  for (int k = 32; k; k >>= 1) {
+    const unsigned long long o = __shfl_xor(low, k);
+    low = o < low ? o : low;
+  }
+  if ((threadIdx.x & 63) == 0 && low != ~0ull) atomicMin(lowest, low);
+}
+
+// Exclusive scans over n entries of `ncols` u64 arrays (column c at a + c *
+// stride), in the three steps of the planner's own scan (zd_k_plan_scan_*):
+// 256-entry tiles in LDS, the tiles' sums by one wave a column, every entry
+// plus its tile's start.  tot: ncols x (ntiles + 1) words, a column's tile
+// starts and then its total.  in32: the (one) column's values, read from
+// there instead of from a.
+__global__ __launch_bounds__(256) void zd_k_scan_tiles(uint64_t* a, const uint32_t* __restrict__ in32, uint64_t n,
+                                                       uint64_t stride, uint64_t* tot) {
+  __shared__ uint64_t s[256];
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  uint64_t* col = a + (uint64_t)blockIdx.y * stride;
+  const uint64_t v = i < n ? (in32 ? (uint64_t)in32[i] : col[i]) : 0;
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const uint64_t p = threadIdx.x >= (unsigned)d ? s[threadIdx.x - d] : 0;
+    __syncthreads();
+    s[threadIdx.x] += p;
+    __syncthreads();
+  }
+  if (i < n) col[i] = s[threadIdx.x] - v;
+  if (threadIdx.x == 255) tot[(uint64_t)blockIdx.y * (gridDim.x + 1) + blockIdx.x] = s[255];
+}
+__global__ __launch_bounds__(64) void zd_k_scan_sums(uint64_t* tot, uint64_t ntiles) {
+  uint64_t* t = tot + (uint64_t)blockIdx.x * (ntiles + 1);
+  const uint32_t lane = threadIdx.x;
+  unsigned long long acc = 0;
+  for (uint64_t base = 0; base < ntiles; base += 64) {
+    const uint64_t k = base + lane;
+    const unsigned long long v = k < ntiles ? t[k] : 0;
+    unsigned long long incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned long long u = __shfl_up(incl, d);
+      if (lane >= (uint32_t)d) incl += u;
+    }
+    if (k < ntiles) t[k] = acc + incl - v;
+    acc += __shfl(incl, 63);
+  }
+  if (lane == 0) t[ntiles] = acc;
+}
+__global__ __launch_bounds__(256) void zd_k_scan_add(uint64_t* a, uint64_t n, uint64_t stride,
+                                                     const uint64_t* __restrict__ tot) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) a[(uint64_t)blockIdx.y * stride + i] += tot[(uint64_t)blockIdx.y * (gridDim.x + 1) + blockIdx.x];
+}
+
+// zd_k_batch_place: destination addresses -> offsets from the lowest one (0
+// for a chunk without a destination); res (lane 0): the layout's totals --
+// gathered bytes, pieces, the lowest destination (0: none).
+__global__ __launch_bounds__(256) void zd_k_batch_place(uint64_t* out, uint32_t n,
+                                                        const unsigned long long* __restrict__ lowest,
+                                                        const uint64_t* __restrict__ tot, uint64_t ntiles,
+                                                        uint64_t* res) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const uint64_t low = *lowest == ~0ull ? 0 : (uint64_t)*lowest;
+  if (i < n) {
+    const uint64_t d = out[i];
+    out[i] = d ? d - low : 0;
+  }
+  if (i == 0) {
+    res[0] = tot[ntiles];
+    res[1] = tot[(ntiles + 1) + ntiles];
+    res[2] = low;
+  }
+}
+
+// zd_k_batch_fit: zd_batch_create's capacity pass, one lane per chunk, on the
+// device index.  A usable Frame_Content_Size above the chunk's capacity:
+// ZD_E_DST_TOO_SMALL here, nothing of the chunk runs; bind[i]: the caller's
+// capacity is below what the plan reserves for a frame without a usable one.
+// A chunk zd_k_batch_layout refused gets its status here.  set_ids (a
+// dictionary set, sorted by ID, `fallback` an index into it or -1): used[k]
+// is set for the set's entry the chunk's frame takes (DictSetData::find).
+__global__ __launch_bounds__(256) void zd_k_batch_fit(HostFrame* frames, const HostBlock* __restrict__ blocks,
+                                                      const uint64_t* __restrict__ cap,
+                                                      const uint8_t* __restrict__ flag, uint32_t n, uint8_t* bind,
+                                                      const uint32_t* __restrict__ set_ids, uint32_t nset,
+                                                      int32_t fallback, uint8_t* used) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  HostFrame& hf = frames[i];
+  uint8_t b = 0;
+  if (flag[i]) {
+    const int code = flag[i] == CHUNK_INVALID ? ZD_E_INVALID_ARG : ZD_E_OUT_OF_DOMAIN;
+    hf.status = code;
+    hf.key = make_key(PH_LIMIT, 0, 0, 0, code);
+  } else if (hf.d.kind == ZD_FRAME_ZSTD && hf.key == KEY_NONE) {
+    uint64_t bound = 0;
+    for (uint32_t k = 0; k < hf.nb; k++) {
+      const HostBlock& hb = blocks[hf.b0 + k];
+      bound += hb.type == 2 ? MAX_BLOCK_OUT : hb.size;
+    }
+    const bool usable = hf.d.content_size != UINT64_MAX && hf.d.content_size <= bound;
+    if (usable && hf.d.content_size > cap[i]) {
+      hf.status = ZD_E_DST_TOO_SMALL;
+      hf.key = make_key(PH_LIMIT, 0, 0, 0, ZD_E_DST_TOO_SMALL);
+    }
+    b = !usable && cap[i] < bound;
+  }
+  bind[i] = b;
+  if (used && hf.d.kind == ZD_FRAME_ZSTD) {
+    int32_t e = -1;
+    if (hf.d.dict_id == UINT64_MAX || hf.d.dict_id == 0) {
+      e = fallback;
+    } else {
+      uint32_t lo = 0, hi = nset;
+      while (lo < hi) {
+        const uint32_t m = lo + (hi - lo) / 2;
+        if (set_ids[m] < hf.d.dict_id) lo = m + 1; else hi = m;
+      }
+      if (lo < nset && set_ids[lo] == hf.d.dict_id) e = (int32_t)lo;
+    }
+    if (e >= 0) used[e] = 1;
+  }
+}
+
+hipError_t launch_scan64(uint64_t* a, const uint32_t* in32, uint64_t n, uint32_t ncols, uint64_t stride, uint64_t* tot,
+                         hipStream_t s) {
+  const uint32_t nt = (uint32_t)((n + 255) / 256);
+  if (nt) hipLaunchKernelGGL(zd_k_scan_tiles, dim3(nt, ncols), dim3(256), 0, s, a, in32, n, stride, tot);
+  hipLaunchKernelGGL(zd_k_scan_sums, dim3(ncols), dim3(64), 0, s, tot, (uint64_t)nt);
+  if (nt) hipLaunchKernelGGL(zd_k_scan_add, dim3(nt, ncols), dim3(256), 0, s, a, n, stride, (const uint64_t*)tot);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_layout(const uint64_t* src, const uint64_t* size, const uint64_t* dst, const uint64_t* cap,
+                               uint32_t n, const BatchArrays& A, uint64_t* scratch, uint64_t* res, hipStream_t s) {
+  if (!n || A.piece0 != A.off + n) return hipErrorInvalidValue;   // (off | piece0: the two scanned columns)
+  const uint32_t nt = (n + 255) / 256;
+  unsigned long long* lowest = (unsigned long long*)(scratch + 2 * ((uint64_t)nt + 1));
+  hipError_t e = hipMemsetAsync(lowest, 0xFF, 8, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(zd_k_batch_layout, dim3(nt), dim3(256), 0, s, src, size, dst, cap, n, A, lowest);
+  e = launch_scan64(A.off, nullptr, n, 2, n, scratch, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(zd_k_batch_place, dim3(nt), dim3(256), 0, s, A.out, n, (const unsigned long long*)lowest,
+                     (const uint64_t*)scratch, (uint64_t)nt, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_scan(const ChunkList& L, uint8_t* gathered, const uint64_t* d_piece0, uint32_t n,
+                              uint64_t npieces, hipStream_t s) {
+  if (!npieces || !n) return hipSuccess;
+  hipLaunchKernelGGL(zd_k_gather_scan, dim3((uint32_t)(npieces * K0_SPLIT)), dim3(256), 0, s, L, gathered, d_piece0, n,
+                     npieces);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_fit(HostFrame* frames, const HostBlock* blocks, const uint64_t* cap, const uint8_t* flag,
+                            uint32_t n, uint8_t* bind, const uint32_t* set_ids, uint32_t nset, int32_t fallback,
+                            uint8_t* used, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(zd_k_batch_fit, dim3((n + 255) / 256), dim3(256), 0, s, frames, blocks, cap, flag, n, bind,
+                     set_ids, nset, fallback, used);
   return hipGetLastError();
 }
 

@@ -84,7 +84,7 @@ hipError_t launch_walk(const uint8_t* src, uint64_t n, uint64_t first, uint64_t 
 struct PlanShape { uint32_t multi, jcand; uint64_t jmaxseq; };
 hipError_t launch_plan_shape(const HostFrame* frames, uint64_t nf, uint32_t k4j_min, PlanShape* out, hipStream_t s);
 hipError_t launch_plan_count(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
-                             uint64_t* cnt, uint64_t* tot, PlanShape* shape, hipStream_t s);
+                             uint64_t* cnt, uint64_t* tot, PlanShape* shape, hipStream_t s, uint32_t dict_comps = 0);
 hipError_t launch_plan_fill(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
                             const uint64_t* cnt, const uint64_t* tot, const Sink& S, hipStream_t s);
 
@@ -112,6 +112,38 @@ hipError_t launch_walk_chunks(const uint8_t* gathered, const ChunkList& L, uint3
 // ZD_E_DST_TOO_SMALL).
 hipError_t launch_batch_results(const FrameState* fstate, const uint8_t* bind, uint32_t n, int32_t* status,
                                 uint64_t* len, hipStream_t s);
+
+// A batch made from device arrays (zd_batch_create_device).  The batch's own
+// per-chunk arrays, n entries each; off and piece0 are adjacent (piece0 == off
+// + n: the layout scans them as two columns).
+struct BatchArrays {
+  uint64_t *src, *size;    // the caller's entries, or 0 / 0 for a refused chunk (flag)
+  uint64_t* off;           // ChunkList::off
+  uint64_t* piece0;        // the chunk's first piece among the batch's (zd_k_gather_scan)
+  uint64_t* out;           // the destination's offset from the lowest destination
+  uint64_t* cap;           // the caller's capacity (0 for a refused chunk)
+  uint8_t* flag;           // CHUNK_*
+};
+enum : uint8_t { CHUNK_OK = 0, CHUNK_INVALID = 1, CHUNK_TOO_LARGE = 2 };
+// zd_k_batch_layout, the scans of off / piece0, zd_k_batch_place.  scratch: 2 *
+// (tiles + 1) + 1 words (tiles of 256 chunks); res[0..3): gathered bytes,
+// pieces, the lowest destination.
+hipError_t launch_batch_layout(const uint64_t* src, const uint64_t* size, const uint64_t* dst, const uint64_t* cap,
+                               uint32_t n, const BatchArrays& A, uint64_t* scratch, uint64_t* res, hipStream_t s);
+// Exclusive scan of n entries of ncols u64 arrays in place (column c at a + c *
+// stride; in32: one column's input instead); tot: ncols x (tiles + 1) words,
+// a column's total last.
+hipError_t launch_scan64(uint64_t* a, const uint32_t* in32, uint64_t n, uint32_t ncols, uint64_t stride, uint64_t* tot,
+                         hipStream_t s);
+// zd_k_gather over the scanned piece starts instead of a piece list
+hipError_t launch_gather_scan(const ChunkList& L, uint8_t* gathered, const uint64_t* d_piece0, uint32_t n,
+                              uint64_t npieces, hipStream_t s);
+// zd_k_batch_fit: the capacity pass over the device index (frames' status /
+// key, bind[]), the refused chunks' statuses, and with set_ids the used flags
+// of a dictionary set's entries.
+hipError_t launch_batch_fit(HostFrame* frames, const HostBlock* blocks, const uint64_t* cap, const uint8_t* flag,
+                            uint32_t n, uint8_t* bind, const uint32_t* set_ids, uint32_t nset, int32_t fallback,
+                            uint8_t* used, hipStream_t s);
 
 constexpr int N_KERNELS = 6;
 // mode-2 launch groups (LaunchArgs::dom_events: events 2g, 2g + 1)

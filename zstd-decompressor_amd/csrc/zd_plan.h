@@ -84,15 +84,16 @@ struct PlanCtx {
   // frame's own bytes).  dict_id: the dictionary's ID (0: raw content).
   bool dict;
   uint32_t dict_id;
-  // Optional per-frame placement (a batch, zd_batch_create; null everywhere
-  // else, the device planner included): frame fi's output starts at
+  // Optional per-frame placement (a batch; null everywhere else): host arrays
+  // in the host planner (zd_batch_create), device arrays in the device planner
+  // (zd_batch_create_device).  Frame fi's output starts at
   // place_out[fi] from the output base instead of the running offset, and its
   // capacity is at most place_cap[fi].
   const uint64_t* place_out;
   const uint64_t* place_cap;
   // Optional dictionary table (a dictionary-set plan, zd_plan_create_dicts /
-  // zd_batch_create_dicts; null everywhere else, the device planner included;
-  // `dict` is set with it): every frame takes out_len0, its first repeat
+  // zd_batch_create_dicts, and on the device zd_batch_create_device_dicts; null
+  // everywhere else; `dict` is set with it): every frame takes out_len0, its first repeat
   // offsets and its previous tables from the entry of its own Dictionary_ID
   // instead of the plan-wide fields above.  A frame without an ID (or with ID
   // 0) takes entry dset_fallback, or none at all when that is -1: it then

@@ -57,7 +57,7 @@ class GatherResult(C.Structure):
 class BatchInfo(C.Structure):
     _fields_ = [("nchunks", C.c_uint64), ("gathered_bytes", C.c_uint64), ("nblocks", C.c_uint64),
                 ("nsequences", C.c_uint64), ("workspace_bytes", C.c_uint64), ("executors", C.c_uint32),
-                ("reserved", C.c_uint32), ("gather_ns", C.c_uint64), ("walk_ns", C.c_uint64),
+                ("device_built", C.c_uint32), ("gather_ns", C.c_uint64), ("walk_ns", C.c_uint64),
                 ("host_ns", C.c_uint64), ("upload_ns", C.c_uint64)]
 
 
@@ -100,6 +100,8 @@ SIGNATURES = {
                                         _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_create": (C.c_int, [C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64), _sz,
                                   C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
+    "zd_batch_create_device": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
+    "zd_batch_create_device_dicts": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_info_get": (C.c_int, [_vp, C.POINTER(BatchInfo)]),
     "zd_batch_decode_async": (C.c_int, [_vp, _vp]),
     "zd_batch_device_results": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

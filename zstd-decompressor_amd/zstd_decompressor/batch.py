@@ -297,6 +297,57 @@ class Batch:
         self.info = _lib.BatchInfo()
         _lib.check(_lib.lib().zd_batch_info_get(h, C.byref(self.info)), "zd_batch_info_get")
 
+    @classmethod
+    def from_device(cls, src_ptrs, src_sizes, dst_ptrs, dst_caps, nchunks=None, flags: int = 0, dictionary=None,
+                    stream: int = 0):
+        """zd_batch_create_device: the same batch from a chunk table that is on
+        the device.  Each of the four arrays is a contiguous int64 / uint64
+        device tensor of one entry a chunk, or the device address of such an
+        array (an integer) with `nchunks` given; they must be readable on
+        `stream` and may be released when this returns.  Layout, walk, capacity
+        checks and descriptors are built on the GPU.  A bad entry (a NULL
+        address with a non-zero count) fails its own chunk with INVALID_ARG
+        instead of the call, and overlapping destinations are not checked: the
+        caller keeps them disjoint.  `.info.device_built` is 1."""
+        arrs = (src_ptrs, src_sizes, dst_ptrs, dst_caps)
+        n, addr, keep = nchunks, [], []
+        for a in arrs:
+            if isinstance(a, int):
+                addr.append(a)
+                continue
+            import torch
+            if not (isinstance(a, torch.Tensor) and a.is_cuda and a.is_contiguous() and a.dim() == 1
+                    and a.dtype in (torch.int64, torch.uint64)):
+                raise ValueError("contiguous 1-D int64 / uint64 device tensors, or device addresses, required")
+            if n is None:
+                n = a.numel()
+            if a.numel() != n:
+                raise ValueError("the arrays and nchunks differ in length")
+            addr.append(a.data_ptr() if n else 0)
+            keep.append(a)
+        if n is None:
+            raise ValueError("nchunks is required when every array is a raw address")
+        if dictionary is not None and not getattr(dictionary, "_h", None):
+            raise ValueError("the %s is closed" % type(dictionary).__name__)
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        sp, ss, dp, dc = (C.c_void_p(a) for a in addr)
+        if isinstance(dictionary, DictionarySet):
+            _lib.check(_lib.lib().zd_batch_create_device_dicts(sp, ss, dp, dc, n, flags, dictionary._h,
+                                                               C.c_void_p(stream), C.byref(h)),
+                       "zd_batch_create_device_dicts")
+        else:
+            _lib.check(_lib.lib().zd_batch_create_device(sp, ss, dp, dc, n, flags,
+                                                         dictionary._h if dictionary else None, C.c_void_p(stream),
+                                                         C.byref(h)),
+                       "zd_batch_create_device")
+        del keep
+        self._h = h
+        self.nchunks = n
+        self.info = _lib.BatchInfo()
+        _lib.check(_lib.lib().zd_batch_info_get(h, C.byref(self.info)), "zd_batch_info_get")
+        return self
+
     def decode_async(self, stream: int = 0):
         """Launch the decode of every chunk (no allocation, no host synchronisation)."""
         _lib.check(_lib.lib().zd_batch_decode_async(self._h, C.c_void_p(stream)), "zd_batch_decode_async")
