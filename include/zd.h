@@ -555,6 +555,101 @@ int  zd_batch_create_device(const void* const* d_src_ptrs, const uint64_t* d_src
 int  zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes,
                                   void* const* d_dst_ptrs, const uint64_t* d_dst_cap, size_t nchunks,
                                   uint32_t flags, const zd_dict_set* set, void* stream, zd_batch** out);
+/* What chunks need of their destinations, asked on the device: chunk i is the
+ * d_src_bytes[i] bytes at d_src_ptrs[i], as in zd_batch_create_device.  All
+ * five arrays are DEVICE arrays of nchunks entries; d_status and d_exact may be
+ * NULL.  The call queues one kernel (zd_k_chunk_sizes, one lane per chunk) on
+ * `stream` and returns: no allocation, no copy, no host synchronisation, so it
+ * can be captured like zd_decode_async.  The chunks are read where they lie, at
+ * any alignment, and exactly the bytes [src, src + size) at most: the caller
+ * owes no ZD_SRC_PADDING.  Per chunk:
+ *   d_size[i]    the chunk's reserve: its frame's Frame_Content_Size when that
+ *                is usable (present and not above `bound`), else `bound` = 128
+ *                KiB per compressed block + the sizes of the raw and RLE
+ *                blocks.  It is the capacity a batch gives the chunk at most,
+ *                so a destination of d_size[i] bytes never makes the chunk
+ *                ZD_E_DST_TOO_SMALL.  0 for a chunk without a zstd frame (no
+ *                bytes, skippable frames only) and for a chunk whose status is
+ *                not ZD_OK.
+ *   d_exact[i]   1: d_size[i] is the Frame_Content_Size (the decoded length of
+ *                a frame that decodes); 0: it is the bound (the decoded length
+ *                is at most that), or 0.
+ *   d_status[i]  what the header walk of that chunk alone gives, with the
+ *                meanings of zd_batch_create_device: ZD_OK; the walk's own code
+ *                (a truncated frame, trailing bytes, a section header that does
+ *                not parse); ZD_E_OUT_OF_DOMAIN at a second zstd frame or for a
+ *                chunk of 2^32 bytes or more; ZD_E_INVALID_ARG for a NULL
+ *                address with a non-zero size or a range that wraps (nothing of
+ *                such a chunk is read).
+ * Errors that only decoding finds are NOT seen here -- a corrupt table
+ * description, a frame that overruns its Frame_Content_Size, a dictionary the
+ * batch does not have: such a chunk is ZD_OK here with its reserve, and fails
+ * when it is decoded.
+ * flags: ZD_SIZES_DICT when the chunks will be decoded with a dictionary or a
+ * set (an empty Raw literals section is then accepted, as in a dictionary
+ * plan; without it such a chunk is ZD_E_EMPTY_SLICE).
+ * ZD_E_INVALID_ARG, before any HIP call: a NULL d_src_ptrs, d_src_bytes or
+ * d_size with nchunks > 0, nchunks >= 2^31, unknown flag bits.  nchunks == 0 is
+ * ZD_OK without a HIP call. */
+#define ZD_SIZES_DICT 1u
+int  zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
+                           uint32_t flags, uint64_t* d_size, int32_t* d_status, uint8_t* d_exact, void* stream);
+/* zd_batch_create_device without destinations: a PACKED batch lays its outputs
+ * out itself, in one buffer that is bound to it afterwards
+ * (zd_batch_bind_output).  Chunk i's capacity is its reserve (what
+ * zd_chunk_sizes_device reports for it) and its place is offset[i] from the
+ * buffer's base: the offsets ascend with i, each is a multiple of `align` (a
+ * power of two in [1, 4096]) and offset[i + 1] >= offset[i] + cap[i];
+ * out_bytes = the sum of the reserves each rounded up to `align`
+ * (zd_batch_output_layout).  Creation is zd_batch_create_device's -- layout,
+ * gather, the two walk passes, then zd_k_batch_pack and one scan for the
+ * places, the capacity pass and the device planner on those two columns -- and
+ * the result is an ordinary batch (device_built = 1) with the routing,
+ * executors, dictionary handling and per-chunk statuses of the batch
+ * zd_batch_create_device makes from the same sources with d_dst[i] = base +
+ * offset[i] and dst_cap[i] = cap[i].  A packed batch never reports
+ * ZD_E_DST_TOO_SMALL from creation.  A frame without a usable
+ * Frame_Content_Size gets its bound and decodes in place at its offset: the
+ * buffer has slack after it, and the lengths (zd_batch_device_results) say how
+ * much; offsets and lengths together are a complete index of the output.
+ * A frame whose reserve passes the executors' limits is that chunk's
+ * ZD_E_OUT_OF_DOMAIN, as in any batch; the 64-bit total cannot wrap (a chunk of
+ * z < 2^32 bytes reserves less than z / 3 * 128 KiB).
+ * Synchronises `stream`: the waits of zd_batch_create_device and none more --
+ * the five that read words back (layout totals, block count, routing shape,
+ * plan totals, the frames' offsets and capacities) and the one after the
+ * gather: the one word of out_bytes comes back with the routing shape.
+ * ZD_E_INVALID_ARG, before any HIP call: what zd_batch_create_device refuses
+ * the call for (without the destination arrays), and an `align` that is not a
+ * power of two in [1, 4096]. */
+int  zd_batch_create_device_packed(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
+                                   uint32_t align, uint32_t flags, const zd_dict* dict, void* stream,
+                                   zd_batch** out);
+/* zd_batch_create_device_packed with a dictionary set (must not be NULL). */
+int  zd_batch_create_device_packed_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
+                                         uint32_t align, uint32_t flags, const zd_dict_set* set, void* stream,
+                                         zd_batch** out);
+/* A packed batch's layout: the bytes its output buffer needs and two device
+ * arrays of nchunks uint64 entries, the chunks' offsets from the base and
+ * their capacities.  The batch owns the arrays; they are valid until
+ * zd_batch_destroy, and work queued on the creation's stream reads them without
+ * a round trip.  Any of the three pointers may be NULL.  ZD_E_INVALID_ARG for a
+ * NULL batch or one that was not made packed. */
+int  zd_batch_output_layout(const zd_batch* batch, uint64_t* out_bytes,
+                            const uint64_t** d_offset, const uint64_t** d_cap);
+/* Binds the packed batch's output buffer: the cap bytes at d_out.  No HIP
+ * call: the base travels as a kernel argument at the next
+ * zd_batch_decode_async.  No alignment is required of d_out (the offsets are
+ * multiples of `align` from the base).  cap < out_bytes is ZD_E_DST_TOO_SMALL
+ * and the previous binding stays; d_out may be NULL only when out_bytes == 0;
+ * a range that wraps, a NULL batch or a batch that was not made packed is
+ * ZD_E_INVALID_ARG.  Binding again is legal and takes effect at the next
+ * zd_batch_decode_async.  zd_batch_results (which decodes a chunk again whose
+ * block-parallel execution did not converge) and zd_batch_checksums work on
+ * the CURRENT binding: call them for a decode before binding another buffer.
+ * zd_batch_decode_async on a packed batch with out_bytes > 0 and no binding is
+ * ZD_E_INVALID_ARG. */
+int  zd_batch_bind_output(zd_batch* batch, void* d_out, uint64_t cap);
 int  zd_batch_info_get(const zd_batch* batch, zd_batch_info* info);
 /* Launches the decode of every chunk on `stream`, ending with a kernel that
  * writes the batch's device result arrays (zd_batch_device_results).  No

@@ -2358,6 +2358,10 @@ struct zd_batch {
   bool device_built = false;
   uint64_t *d_cap = nullptr, *d_piece0 = nullptr;
   uint8_t* d_flag = nullptr;
+  // a packed batch (zd_batch_create_device_packed): d_out / d_cap are its own
+  // layout, outbase the bound buffer (zd_batch_bind_output; null until then)
+  bool packed = false;
+  uint64_t out_bytes = 0;
   int host_arrays() {
     if (!device_built || goff.size() == n) return 0;
     std::vector<uint64_t> o(n), z(n), d(n), c(n);
@@ -2602,12 +2606,17 @@ int zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes, v
 // descriptors all run there; the host reads back a few words a phase (the
 // layout's totals, the block count, the routing shape and a set's used flags,
 // the plan's totals) and the frames' output offsets and capacities.
+// align != 0: a packed batch (zd_batch_create_device_packed): no destination
+// arrays; after the fill pass zd_k_batch_pack and one scan write the chunks'
+// capacities (their reserves) and offsets into d_cap / d_out, and the capacity
+// pass and the planner run on those.
 static int batch_create_device(const void* const* d_src, const uint64_t* d_src_bytes, void* const* d_dst,
                                const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
-                               const zd_dict_set* set, void* stream, zd_batch** out) {
+                               const zd_dict_set* set, void* stream, zd_batch** out, uint32_t align = 0) {
   // ---- argument checks: no HIP call before they are done ----
+  const bool packed = align != 0;
   if (!out || (flags & ZD_F_SKIPPABLE)) return ZD_E_INVALID_ARG;
-  if (nchunks && (!d_src || !d_src_bytes || !d_dst || !d_dst_cap)) return ZD_E_INVALID_ARG;
+  if (nchunks && (!d_src || !d_src_bytes || (!packed && (!d_dst || !d_dst_cap)))) return ZD_E_INVALID_ARG;
   if (nchunks >= (1ull << 31) || (dict && !dict->p) || (set && !set->p)) return ZD_E_INVALID_ARG;
   const size_t n = nchunks;
   zd_batch* B = new (std::nothrow) zd_batch();
@@ -2617,6 +2626,7 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
   B->n = n;
   B->flags = flags;
   B->device_built = true;
+  B->packed = packed;
   B->info.nchunks = n;
   B->info.device_built = 1;
   if (!n) { *out = hold.release(); return ZD_OK; }
@@ -2698,6 +2708,14 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
   WB.bytes = bytes;
   HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, B->d_boff, (HostFrame*)WB.d_out,
                             (HostBlock*)(WB.d_out + fb), true, s));
+  if (packed) {
+    // the chunks' reserves and places; the total comes back with the routing shape (build_plan_device's
+    // first wait), in a pinned word the planner does not use
+    HIPCHK(launch_batch_pack((const HostFrame*)WB.d_out, (const HostBlock*)(WB.d_out + fb), B->d_flag, (uint32_t)n,
+                             align, B->d_cap, B->d_out, s));
+    HIPCHK(launch_scan64(B->d_out, nullptr, n, 1, n, d_scratch, s));
+    HIPCHK(hipMemcpyAsync(WB.h_small + 63, d_scratch + nt, 8, hipMemcpyDeviceToHost, s));
+  }
   // a dictionary set: its IDs go up, the used flags of its entries come back with the routing shape
   struct Free { void operator()(void* p) const { if (p) (void)hipFree(p); } };
   std::unique_ptr<void, Free> set_mem;
@@ -2730,6 +2748,7 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
 
   // ---- descriptors (zd_k_plan_*), placed at the chunks' destinations ----
   if (int r = build_plan_device(P, WB, n, s, &in)) return r;
+  if (packed) B->out_bytes = WB.h_small[63];
   P->index_stop = P->nframes;
   P->info.src_bytes = total;
   const auto t3 = std::chrono::steady_clock::now();
@@ -2763,6 +2782,51 @@ int zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t* 
   return batch_create_device(d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, nchunks, flags, nullptr, set, stream, out);
 }
 
+static bool pack_align_ok(uint32_t align) { return align && align <= 4096 && !(align & (align - 1)); }
+
+int zd_batch_create_device_packed(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
+                                  uint32_t align, uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out) {
+  if (!pack_align_ok(align)) return ZD_E_INVALID_ARG;
+  return batch_create_device(d_src_ptrs, d_src_bytes, nullptr, nullptr, nchunks, flags, dict, nullptr, stream, out,
+                             align);
+}
+
+int zd_batch_create_device_packed_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
+                                        uint32_t align, uint32_t flags, const zd_dict_set* set, void* stream,
+                                        zd_batch** out) {
+  if (!set || !pack_align_ok(align)) return ZD_E_INVALID_ARG;
+  return batch_create_device(d_src_ptrs, d_src_bytes, nullptr, nullptr, nchunks, flags, nullptr, set, stream, out,
+                             align);
+}
+
+int zd_batch_output_layout(const zd_batch* B, uint64_t* out_bytes, const uint64_t** d_offset, const uint64_t** d_cap) {
+  if (!B || !B->packed) return ZD_E_INVALID_ARG;
+  if (out_bytes) *out_bytes = B->out_bytes;
+  if (d_offset) *d_offset = B->d_out;
+  if (d_cap) *d_cap = B->d_cap;
+  return ZD_OK;
+}
+
+int zd_batch_bind_output(zd_batch* B, void* d_out, uint64_t cap) {
+  if (!B || !B->packed) return ZD_E_INVALID_ARG;
+  const uint64_t a = (uint64_t)(uintptr_t)d_out;
+  if ((!d_out && B->out_bytes) || a + cap < a) return ZD_E_INVALID_ARG;
+  if (cap < B->out_bytes) return ZD_E_DST_TOO_SMALL;
+  B->outbase = (uint8_t*)d_out;
+  B->goff.clear();                        // (host_arrays: the chunks' addresses follow the binding)
+  return ZD_OK;
+}
+
+int zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks, uint32_t flags,
+                          uint64_t* d_size, int32_t* d_status, uint8_t* d_exact, void* stream) {
+  if ((flags & ~ZD_SIZES_DICT) || nchunks >= (1ull << 31)) return ZD_E_INVALID_ARG;
+  if (nchunks && (!d_src_ptrs || !d_src_bytes || !d_size)) return ZD_E_INVALID_ARG;
+  if (!nchunks) return ZD_OK;
+  HIPCHK(launch_chunk_sizes((const uint64_t*)d_src_ptrs, d_src_bytes, (uint32_t)nchunks, (flags & ZD_SIZES_DICT) != 0,
+                            d_size, d_status, d_exact, (hipStream_t)stream));
+  return ZD_OK;
+}
+
 int zd_batch_info_get(const zd_batch* B, zd_batch_info* info) {
   if (!B || !info) return ZD_E_INVALID_ARG;
   *info = B->info;
@@ -2772,6 +2836,7 @@ int zd_batch_info_get(const zd_batch* B, zd_batch_info* info) {
 int zd_batch_decode_async(zd_batch* B, void* stream) {
   if (!B) return ZD_E_INVALID_ARG;
   if (!B->P) return ZD_OK;
+  if (B->packed && !B->outbase && B->out_bytes) return ZD_E_INVALID_ARG;   // (no zd_batch_bind_output yet)
   const hipStream_t s = (hipStream_t)stream;
   zd_plan* P = B->P;
   // every frame at its own destination from the lowest one: never the plan's

@@ -6469,7 +6469,8 @@ __global__ __launch_bounds__(256) void zd_k_batch_layout(const uint64_t* __restr
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   unsigned long long low = ~0ull;
   if (i < n) {
-    uint64_t s = src[i], z = size[i], d = dst[i], c = cap[i];
+    // (a packed batch has no destination arrays: its places come from zd_k_batch_pack)
+    uint64_t s = src[i], z = size[i], d = dst ? dst[i] : 0, c = cap ? cap[i] : 0;
     uint8_t flag = CHUNK_OK;
     if ((!s && z) || (!d && c) || s + z < s || d + c < d) flag = CHUNK_INVALID;
     else if (z >= (1ull << 32)) flag = CHUNK_TOO_LARGE;
@@ -6578,11 +6579,7 @@ __global__ __launch_bounds__(256) void zd_k_batch_fit(HostFrame* frames, const H
     hf.status = code;
     hf.key = make_key(PH_LIMIT, 0, 0, 0, code);
   } else if (hf.d.kind == ZD_FRAME_ZSTD && hf.key == KEY_NONE) {
-    uint64_t bound = 0;
-    for (uint32_t k = 0; k < hf.nb; k++) {
-      const HostBlock& hb = blocks[hf.b0 + k];
-      bound += hb.type == 2 ? MAX_BLOCK_OUT : hb.size;
-    }
+    const uint64_t bound = frame_bound(hf, blocks);
     const bool usable = hf.d.content_size != UINT64_MAX && hf.d.content_size <= bound;
     if (usable && hf.d.content_size > cap[i]) {
       hf.status = ZD_E_DST_TOO_SMALL;
@@ -6605,6 +6602,67 @@ __global__ __launch_bounds__(256) void zd_k_batch_fit(HostFrame* frames, const H
     }
     if (e >= 0) used[e] = 1;
   }
+}
+
+// zd_k_batch_pack (zd_batch_create_device_packed): chunk i's reserve
+// (zd_walk.h chunk_reserve, on the filled device index) into cap[i], and the
+// reserve rounded up to `align` (a power of two) into out[i], the column the
+// scan turns into the chunk's offset from the batch's base.  A chunk
+// zd_k_batch_layout refused reserves nothing.
+__global__ __launch_bounds__(256) void zd_k_batch_pack(const HostFrame* __restrict__ frames,
+                                                       const HostBlock* __restrict__ blocks,
+                                                       const uint8_t* __restrict__ flag, uint32_t n, uint64_t align,
+                                                       uint64_t* cap, uint64_t* out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint64_t r = 0;
+  if (!flag[i]) {
+    uint8_t exact;
+    const HostFrame& hf = frames[i];
+    r = chunk_reserve(hf, frame_bound(hf, blocks), &exact);
+  }
+  cap[i] = r;
+  out[i] = (r + align - 1) & ~(align - 1);
+}
+
+// zd_k_chunk_sizes (zd_chunk_sizes_device): the header walk of chunk i where it
+// lies, one lane per chunk, 64 chunks a wave (zd_k_walk_chunks' shape, without
+// the gathered copy): its reserve, the walk's status, whether the reserve is
+// the frame's own Frame_Content_Size.  An entry zd_k_batch_layout would refuse
+// is not read at all.  Byte loads at the chunk's own alignment, nothing outside
+// [src, src + size) (zd_walk.h chunk_size_query).
+__global__ __launch_bounds__(64) void zd_k_chunk_sizes(const uint64_t* __restrict__ src,
+                                                      const uint64_t* __restrict__ size, uint32_t n,
+                                                      bool rfc_empty_lits, uint64_t* out_size, int32_t* status,
+                                                      uint8_t* exact) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t s = src[i], z = size[i];
+  uint64_t r = 0;
+  uint8_t ex = 0;
+  int st = 0;
+  if ((!s && z) || s + z < s) st = ZD_E_INVALID_ARG;
+  else if (z >= (1ull << 32)) st = ZD_E_OUT_OF_DOMAIN;
+  else if (z) st = chunk_size_query((const uint8_t*)(uintptr_t)s, (size_t)z, rfc_empty_lits, &r, &ex);
+  out_size[i] = r;
+  if (status) status[i] = st;
+  if (exact) exact[i] = ex;
+}
+
+hipError_t launch_batch_pack(const HostFrame* frames, const HostBlock* blocks, const uint8_t* flag, uint32_t n,
+                             uint32_t align, uint64_t* cap, uint64_t* out, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(zd_k_batch_pack, dim3((n + 255) / 256), dim3(256), 0, s, frames, blocks, flag, n, (uint64_t)align,
+                     cap, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_chunk_sizes(const uint64_t* src, const uint64_t* size, uint32_t n, bool rfc_empty_lits,
+                              uint64_t* out_size, int32_t* status, uint8_t* exact, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(zd_k_chunk_sizes, dim3((n + 63) / 64), dim3(64), 0, s, src, size, n, rfc_empty_lits, out_size,
+                     status, exact);
+  return hipGetLastError();
 }
 
 hipError_t launch_scan64(uint64_t* a, const uint32_t* in32, uint64_t n, uint32_t ncols, uint64_t stride, uint64_t* tot,

@@ -135,6 +135,15 @@ hipError_t launch_batch_layout(const uint64_t* src, const uint64_t* size, const 
 // a column's total last.
 hipError_t launch_scan64(uint64_t* a, const uint32_t* in32, uint64_t n, uint32_t ncols, uint64_t stride, uint64_t* tot,
                          hipStream_t s);
+// zd_k_batch_pack (a packed batch): cap[i] = chunk i's reserve from the filled
+// device index (0 for a refused chunk), out[i] = it rounded up to `align` (a
+// power of two), to be scanned into the chunk's offset.
+hipError_t launch_batch_pack(const HostFrame* frames, const HostBlock* blocks, const uint8_t* flag, uint32_t n,
+                             uint32_t align, uint64_t* cap, uint64_t* out, hipStream_t s);
+// zd_k_chunk_sizes: one lane per chunk, read in place: reserve, walk status and
+// exact flag per chunk (status / exact may be null).
+hipError_t launch_chunk_sizes(const uint64_t* src, const uint64_t* size, uint32_t n, bool rfc_empty_lits,
+                              uint64_t* out_size, int32_t* status, uint8_t* exact, hipStream_t s);
 // zd_k_gather over the scanned piece starts instead of a piece list
 hipError_t launch_gather_scan(const ChunkList& L, uint8_t* gathered, const uint64_t* d_piece0, uint32_t n,
                               uint64_t npieces, hipStream_t s);

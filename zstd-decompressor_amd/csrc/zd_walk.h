@@ -367,6 +367,59 @@ ZD_HD inline int index_chunk(const uint8_t* base, Bytes& in, HostFrame* hf, SINK
   return 0;
 }
 
+// What a chunk needs of its destination: its reserve (zd_chunk_sizes_device,
+// zd_batch_create_device_packed; the capacity pass of every batch checks
+// against the same numbers).  `bound` is the sum over the frame's blocks of
+// MAX_BLOCK_OUT for a compressed block, else the block's size; the frame's
+// Frame_Content_Size is usable when present and <= bound.  The reserve is the
+// usable Frame_Content_Size (*exact = 1), else bound (*exact = 0); a chunk
+// without a zstd frame (no bytes, skippable frames only) or one the walk failed
+// reserves nothing (0, *exact = 0).
+ZD_HD inline uint64_t frame_bound(const HostFrame& hf, const HostBlock* blocks) {
+  uint64_t bound = 0;
+  for (uint32_t k = 0; k < hf.nb; k++) {
+    const HostBlock& hb = blocks[hf.b0 + k];
+    bound += hb.type == 2 ? MAX_BLOCK_OUT : hb.size;
+  }
+  return bound;
+}
+ZD_HD inline uint64_t chunk_reserve(const HostFrame& hf, uint64_t bound, uint8_t* exact) {
+  *exact = 0;
+  if (hf.d.kind != ZD_FRAME_ZSTD || hf.key != KEY_NONE) return 0;
+  const bool usable = hf.d.content_size != UINT64_MAX && hf.d.content_size <= bound;
+  *exact = usable ? 1 : 0;
+  return usable ? hf.d.content_size : bound;
+}
+
+// A block sink that keeps the frame's bound and block count and no block:
+// index_chunk over it gives a chunk's reserve with no index stored (the
+// skippable frames of a chunk never reach a chunk's sink, index_chunk steps
+// over them with NoBlocks).  It touches no byte of the chunk itself: the walk
+// over it reads what Bytes hands out, nothing else.
+struct WalkBound {
+  uint64_t bound = 0;
+  uint32_t n = 0;
+  ZD_HD size_t size() const { return n; }
+  ZD_HD void push(const HostBlock& hb) {
+    n++;
+    bound += hb.type == 2 ? MAX_BLOCK_OUT : hb.size;
+  }
+};
+
+// One chunk's size query: the header walk of [src, src + size) in place
+// (base = in.p = src, so every read is inside the chunk: Bytes is bounds-checked
+// and index_chunk peeks four bytes only when four are left), the walk's status
+// and the reserve.
+ZD_HD inline int chunk_size_query(const uint8_t* src, size_t size, bool rfc_empty_lits, uint64_t* reserve,
+                                  uint8_t* exact) {
+  Bytes in{src, size};
+  HostFrame hf;
+  WalkBound sink;
+  const int st = index_chunk(src, in, &hf, sink, rfc_empty_lits);
+  *reserve = chunk_reserve(hf, sink.bound, exact);
+  return st;
+}
+
 ZD_HD inline bool magic_word(uint32_t m) { return m == MAGIC_ZSTD || (m ^ MAGIC_SKIP) <= 0x0F; }
 
 // The device walk's per-range summary (zd_k_walk, count pass): where the

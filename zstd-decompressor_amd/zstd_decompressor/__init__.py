@@ -8,7 +8,8 @@ Module map (reference -> here):
   decoding_context.rs -> decoding_context  DecodingContext (GPU-resident)
   decoders/, literals.rs, sequences.rs -> HIP kernels behind the C ABI (include/zd.h)
 Batch API (the hot path): batch.decompress / batch.Plan; batch.Batch for
-scattered device chunks with per-chunk buffers and statuses.
+scattered device chunks with per-chunk buffers and statuses; batch.chunk_sizes /
+Batch.packed / batch.decompress_tensors when the decoded sizes are not known.
 """
 from . import _lib
 from ._lib import ZdError
@@ -16,9 +17,10 @@ from .parsing import ForwardByteParser
 from .frame import Frame, FrameIterator, Header, Skippable, ZStandard, MAX_WIN_SIZE
 from .block import Block
 from .decoding_context import DecodingContext
-from .batch import Batch, Dictionary, DictionarySet, Plan, decode_tensors, decompress, frames_index
+from .batch import (Batch, Dictionary, DictionarySet, Plan, chunk_sizes, decode_tensors, decompress,
+                    decompress_tensors, frames_index)
 
 __all__ = ["ZdError", "ForwardByteParser", "Frame", "FrameIterator", "Header", "Skippable", "ZStandard",
            "MAX_WIN_SIZE", "Block", "DecodingContext", "Batch", "Dictionary", "DictionarySet",
-           "Plan", "decode_tensors", "decompress",
+           "Plan", "chunk_sizes", "decode_tensors", "decompress", "decompress_tensors",
            "frames_index"]

@@ -102,6 +102,12 @@ SIGNATURES = {
                                   C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_create_device": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_create_device_dicts": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
+    "zd_chunk_sizes_device": (C.c_int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "zd_batch_create_device_packed": (C.c_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
+    "zd_batch_create_device_packed_dicts": (C.c_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp,
+                                                      C.POINTER(_vp)]),
+    "zd_batch_output_layout": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(_vp)]),
+    "zd_batch_bind_output": (C.c_int, [_vp, _vp, C.c_uint64]),
     "zd_batch_info_get": (C.c_int, [_vp, C.POINTER(BatchInfo)]),
     "zd_batch_decode_async": (C.c_int, [_vp, _vp]),
     "zd_batch_device_results": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -244,4 +250,5 @@ F_K1_LANES = 64        # K1's sequence half on serial lanes in plans of <= 16,38
 F_J_ONE_ROUND = 128    # test switch: K4J pointer jumping cut to one round of one hop
 F_SEQ_NO_LATENCY = 256 # K3Q instead of the one-block-per-wave K3L in plans of few blocks
 F_K1_SPLIT = 512       # K1 as a parse pass and a build pass in a plan of any size
-EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4   # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)
+SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
+EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)

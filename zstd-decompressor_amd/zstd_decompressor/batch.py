@@ -263,6 +263,62 @@ def _u64_array(values, n: int):
     return (C.c_uint64 * n).from_buffer(a) if n else (C.c_uint64 * 1)()
 
 
+def _device_arrays(arrs, nchunks):
+    """(n, device addresses, tensors to keep) of per-chunk arrays given as
+    contiguous 1-D int64 / uint64 device tensors, device addresses (with
+    nchunks), or Python lists, which are uploaded as one int64 tensor each (the
+    upload is waited for, so the arrays are readable on any stream)."""
+    import torch
+    n, addr, keep, uploaded = nchunks, [], [], False
+    for a in arrs:
+        if isinstance(a, int):
+            addr.append(a)
+            continue
+        if isinstance(a, (list, tuple)):
+            a = torch.tensor([int(v or 0) for v in a], dtype=torch.int64,
+                             device=torch.device("cuda", torch.cuda.current_device()))
+            uploaded = True
+        if not (isinstance(a, torch.Tensor) and a.is_cuda and a.is_contiguous() and a.dim() == 1
+                and a.dtype in (torch.int64, torch.uint64)):
+            raise ValueError("contiguous 1-D int64 / uint64 device tensors, device addresses or lists required")
+        if n is None:
+            n = a.numel()
+        if a.numel() != n:
+            raise ValueError("the arrays and nchunks differ in length")
+        addr.append(a.data_ptr() if n else 0)
+        keep.append(a)
+    if n is None:
+        raise ValueError("nchunks is required when every array is a raw address")
+    if uploaded:
+        torch.cuda.current_stream().synchronize()
+    return n, addr, keep
+
+
+def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, stream=None):
+    """zd_chunk_sizes_device: what each chunk needs of its destination, asked
+    on the device.  src_ptrs / src_sizes as in Batch.from_device (device
+    tensors, or addresses with `nchunks`).  Returns three device tensors
+    (sizes int64, statuses int32, exact uint8): a chunk's reserve (its usable
+    Frame_Content_Size, exact 1, else 128 KiB per compressed block + its raw
+    and RLE blocks, exact 0; 0 for a failing or empty chunk) and the status of
+    its header walk.  dictionary=True when the chunks will be decoded with a
+    Dictionary or DictionarySet.  The kernel is queued on `stream` (torch's
+    current stream by default) and nothing is synchronised."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    n, addr, keep = _device_arrays((src_ptrs, src_sizes), nchunks)
+    dev = keep[0].device if keep else torch.device("cuda", torch.cuda.current_device())
+    sizes = torch.empty(n, dtype=torch.int64, device=dev)
+    statuses = torch.empty(n, dtype=torch.int32, device=dev)
+    exact = torch.empty(n, dtype=torch.uint8, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr() if n else 0)
+    _lib.check(_lib.lib().zd_chunk_sizes_device(C.c_void_p(addr[0]), C.c_void_p(addr[1]), n,
+                                                _lib.SIZES_DICT if dictionary else 0, ptr(sizes), ptr(statuses),
+                                                ptr(exact), C.c_void_p(stream)), "zd_chunk_sizes_device")
+    return sizes, statuses, exact
+
+
 class Batch:
     """zd_batch: N independently compressed chunks at N device addresses, each
     decoded into its own device buffer with its own status (dictionary: a
@@ -348,6 +404,71 @@ class Batch:
         _lib.check(_lib.lib().zd_batch_info_get(h, C.byref(self.info)), "zd_batch_info_get")
         return self
 
+    @classmethod
+    def packed(cls, src_ptrs, src_sizes, nchunks=None, align: int = 16, flags: int = 0, dictionary=None,
+               stream: int = 0):
+        """zd_batch_create_device_packed: a batch made from sources only, which
+        lays its outputs out itself in one buffer.  src_ptrs / src_sizes as in
+        from_device (device tensors, or addresses with `nchunks`); Python lists
+        are uploaded as one int64 tensor each.  Chunk i's capacity is its
+        reserve (chunk_sizes) and its place a multiple of `align` (a power of
+        two up to 4096) from the buffer's base: `.out_bytes` is the buffer's
+        size, output_layout() the two device arrays, bind_output() gives the
+        buffer.  A frame without a usable Frame_Content_Size gets its bound, so
+        there is slack after it: results() tells the lengths."""
+        n, addr, keep = _device_arrays((src_ptrs, src_sizes), nchunks)
+        if dictionary is not None and not getattr(dictionary, "_h", None):
+            raise ValueError("the %s is closed" % type(dictionary).__name__)
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        sp, ss = (C.c_void_p(a) for a in addr)
+        if isinstance(dictionary, DictionarySet):
+            _lib.check(_lib.lib().zd_batch_create_device_packed_dicts(sp, ss, n, align, flags, dictionary._h,
+                                                                      C.c_void_p(stream), C.byref(h)),
+                       "zd_batch_create_device_packed_dicts")
+        else:
+            _lib.check(_lib.lib().zd_batch_create_device_packed(sp, ss, n, align, flags,
+                                                                dictionary._h if dictionary else None,
+                                                                C.c_void_p(stream), C.byref(h)),
+                       "zd_batch_create_device_packed")
+        del keep
+        self._h = h
+        self.nchunks = n
+        self.info = _lib.BatchInfo()
+        _lib.check(_lib.lib().zd_batch_info_get(h, C.byref(self.info)), "zd_batch_info_get")
+        ob = C.c_uint64()
+        _lib.check(_lib.lib().zd_batch_output_layout(h, C.byref(ob), None, None), "zd_batch_output_layout")
+        self.out_bytes = ob.value
+        return self
+
+    def output_layout(self):
+        """A packed batch's (device address of the uint64 offsets, device address
+        of the uint64 capacities), nchunks entries each, owned by the batch."""
+        off, cap = C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.lib().zd_batch_output_layout(self._h, None, C.byref(off), C.byref(cap)),
+                   "zd_batch_output_layout")
+        return off.value or 0, cap.value or 0
+
+    def bind_output(self, out, cap=None):
+        """zd_batch_bind_output: the packed batch decodes into `out`, a
+        contiguous uint8 device tensor or a device address with `cap` bytes.
+        Takes effect at the next decode_async; call results() / checksums() of
+        a decode before binding another buffer."""
+        if isinstance(out, int):
+            if cap is None:
+                raise ValueError("cap is required with a raw address")
+            ptr = out
+        else:
+            import torch
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8):
+                raise ValueError("a contiguous uint8 device tensor, or a device address with cap, required")
+            ptr = out.data_ptr() if out.numel() else 0
+            if cap is None:
+                cap = out.numel()
+            elif cap > out.numel():
+                raise ValueError("cap exceeds the tensor")
+        _lib.check(_lib.lib().zd_batch_bind_output(self._h, C.c_void_p(ptr), cap), "zd_batch_bind_output")
+
     def decode_async(self, stream: int = 0):
         """Launch the decode of every chunk (no allocation, no host synchronisation)."""
         _lib.check(_lib.lib().zd_batch_decode_async(self._h, C.c_void_p(stream)), "zd_batch_decode_async")
@@ -405,5 +526,49 @@ def decode_tensors(srcs, dsts, dictionary=None, flags: int = 0):
     try:
         b.decode_async(stream)
         return b.results(stream)
+    finally:
+        b.close()
+
+
+def _read_u64(d_ptr: int, n: int):
+    """n uint64 words at a device address, as a list (a blocking hipMemcpy of
+    the HIP runtime the process already runs: torch's own, else the system's)."""
+    import os
+    import torch
+    if not n:
+        return []
+    rt = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
+    hip = C.CDLL(rt if os.path.exists(rt) else "libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipMemcpy.restype = C.c_int
+    words = (C.c_uint64 * n)()
+    if hip.hipMemcpy(words, C.c_void_p(d_ptr), 8 * n, 2) != 0:     # hipMemcpyDeviceToHost
+        raise ZdError(_lib.HIP, "hipMemcpy")
+    return list(words)
+
+
+def decompress_tensors(srcs, dictionary=None, flags: int = 0, align: int = 16):
+    """Decode uint8 device tensors srcs[i] (one chunk each) without knowing
+    their sizes: a packed batch (Batch.packed) over them, one uint8 tensor of
+    its out_bytes, the decode on torch's current stream.  Returns (outs,
+    statuses): outs[i] is a view of chunk i's decoded bytes in that tensor at
+    the chunk's offset (a multiple of `align`), empty for a failing chunk."""
+    import torch
+    for t in srcs:
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("contiguous uint8 device tensors required")
+    n = len(srcs)
+    dev = srcs[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream().cuda_stream
+    b = Batch.packed([t.data_ptr() if t.numel() else 0 for t in srcs], [t.numel() for t in srcs], align=align,
+                     flags=flags, dictionary=dictionary, stream=stream)
+    try:
+        out = torch.empty(b.out_bytes, dtype=torch.uint8, device=dev)
+        b.bind_output(out)
+        b.decode_async(stream)
+        statuses, lengths = b.results(stream)
+        offs = _read_u64(b.output_layout()[0], n)
+        outs = [out[offs[i]:offs[i] + lengths[i]] for i in range(n)]
+        return outs, statuses
     finally:
         b.close()
