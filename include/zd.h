@@ -78,6 +78,8 @@ extern "C" {
                                       a repeat offset of 0 or past the content, or without content */
 #define ZD_E_DICT_MISMATCH   (-99) /* a frame names a Dictionary_ID other than the plan's dictionary's
                                       (a dictionary set: an ID the set does not hold) */
+#define ZD_E_CHECKSUM_WRONG  (-100) /* ZD_F_VERIFY_CHECKSUM: the frame decoded, and its bytes do not hash to its
+                                       Content_Checksum (libzstd: "Restored data doesn't match checksum") */
 
 /* Device workspaces of destroyed plans are kept for reuse by later plans of
  * the process (bounded by ZD_WS_CACHE_MB, default 8 GiB; 0 disables it).
@@ -178,6 +180,36 @@ typedef struct zd_plan zd_plan;
  * whose match chains are deeper keys LS_JROUNDS and zd_plan_decompress plans
  * it again on the streaming executor (tests/test_large_frames.py). */
 #define ZD_F_J_ONE_ROUND 128u
+/* Verify Content_Checksums inside the decode launch (opt-in; the default keeps
+ * the reference's behaviour, which hashes and never enforces).  A
+ * plan / batch flag, accepted wherever plan flags are: zd_plan_create, _dict,
+ * _dicts, _device, zd_decompress*, every zd_batch_create*, and the sharded
+ * calls, which pass it to their plans.  With it zd_decode_async /
+ * zd_batch_decode_async end with one more kernel (zd_k_verify; only when some
+ * zstd frame of the plan carries a Content_Checksum) behind everything else
+ * they queue: no host work, no allocation, no synchronisation, capturable
+ * like a launch without the flag.  After a frame's last block has executed, a
+ * zstd frame that carries a Content_Checksum, whose status is ZD_OK, and whose
+ * decoded bytes' XXH64 (seed 0) differs in its low 32 bits from the stored
+ * value gets ZD_E_CHECKSUM_WRONG:
+ *  - in a plan it is a failing frame like any other: the output stops before
+ *    it, later frames are ZD_E_NOT_DECODED, first_error_frame names it
+ *    (zd_plan_decompress's re-plans keep the flag);
+ *  - in a batch that chunk alone fails, with length 0; the bytes stay in its
+ *    buffer, unspecified (the streaming re-decode inside zd_batch_results of a
+ *    chunk whose block-parallel execution did not converge verifies too);
+ *  - a frame that already failed keeps its own status: the check never
+ *    replaces another error and never reads a failed frame's bytes;
+ *  - a frame without a Content_Checksum, and a skippable frame, is unaffected;
+ *  - an empty checksummed frame verifies (XXH64 of no bytes is
+ *    0xEF46DB3751D8E999).
+ * Without the flag nothing changes: the same launches, the same statuses.
+ * zd_plan_checksums / zd_batch_checksums behave the same with and without it;
+ * on a verified plan they report ok = -1 for a frame that failed
+ * verification (and for the frames after it), as for any frame that was not
+ * decoded.  zd_context / zd_block_decode / zd_execute_sequences take no flags
+ * and stay outside the feature. */
+#define ZD_F_VERIFY_CHECKSUM 1024u
 
 /* zd_plan_info.executors: */
 #define ZD_EXEC_FUSED 1u   /* zd_k_fused: tables, FSE chains and execution per group of four
@@ -281,7 +313,10 @@ int zd_plan_results(zd_plan* plan, uint8_t* d_dst, void* stream,
  * it equals the digest's low 32 bits, 0 when it differs, -1 when the frame has
  * none or was not decoded; hash[i] = the digest (0 if not decoded).  The
  * reference computes the hash but never enforces it (frame.rs:239-255,
- * SURVEY D5), so a mismatch never changes the decode status.  Host arrays of
+ * SURVEY D5), so a mismatch never changes the decode status (a plan made with
+ * ZD_F_VERIFY_CHECKSUM enforces it inside the launch instead; this call is
+ * the same with and without the flag, and there reports -1 for the frame that
+ * failed verification, which was not decoded).  Host arrays of
  * plan nframes entries, either may be NULL. */
 int zd_plan_checksums(zd_plan* plan, const uint8_t* d_dst, void* stream, int32_t* ok, uint64_t* hash);
 
@@ -661,6 +696,18 @@ int  zd_batch_decode_async(zd_batch* batch, void* stream);
  * d_len[i] its decoded length (0 unless ZD_OK).  Work queued behind it on the
  * same stream reads them without a host round trip. */
 int  zd_batch_device_results(const zd_batch* batch, const int32_t** d_status, const uint64_t** d_len);
+/* A ZD_F_VERIFY_CHECKSUM batch's device checksum arrays, owned by the batch
+ * (nchunks entries each) and written by the verification pass of
+ * zd_batch_decode_async, before the result arrays: d_hash[i] is the full 64-bit
+ * XXH64 of chunk i's decoded bytes, or 0 for a chunk that did not decode or
+ * carries no Content_Checksum (the pass reads only the frames it checks; a
+ * chunk that fails verification keeps its digest); d_ok[i] is 1 / 0 / -1 with
+ * zd_batch_checksums' meanings (matches / differs / no Content_Checksum or not
+ * decoded).  Work queued behind the decode on the same stream reads them
+ * without a host round trip.  Either pointer may be NULL; a batch of no chunks
+ * gives NULL arrays.  ZD_E_INVALID_ARG for a NULL batch or one made without
+ * the flag. */
+int  zd_batch_device_checksums(const zd_batch* batch, const uint64_t** d_hash, const int8_t** d_ok);
 /* Waits for `stream` and returns the same arrays (host arrays of cap >=
  * nchunks entries, either may be NULL) and the number of chunks that are not
  * ZD_OK.  A chunk whose block-parallel execution did not converge (K4J's

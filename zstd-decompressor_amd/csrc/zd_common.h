@@ -313,6 +313,10 @@ enum : uint32_t { PH_PARSE = 0, PH_DECODE = 1, PH_LIMIT = 3 };
 enum : uint32_t { PS_STRUCT = 0, PS_HUF_DESC = 1, PS_JUMP = 2, PS_SEQ_HDR = 3, PS_SEQ_TABLES = 4, PS_ALL = 5 };
 // decode stages inside Block::decode (block.rs:80-87)
 enum : uint32_t { DS_LITERALS = 1, DS_SEQUENCES = 2, DS_EXECUTE = 3 };
+// after a frame's last block (block = the frame's block count): the decoded
+// bytes do not hash to the frame's Content_Checksum (ZD_F_VERIFY_CHECKSUM,
+// zd_k_verify; the only key written onto a frame that decoded)
+constexpr uint32_t DS_CHECKSUM = 4;
 // PH_LIMIT stages the host can act on: a frame that decodes past the capacity
 // its plan reserved (re-planned with more, zd_plan_decompress), K4J's
 // pointer jumping not converging within its rounds (re-planned streaming)
@@ -487,6 +491,9 @@ struct Workspace {
   // dictionary-set plans only (0 elsewhere): u32 per frame, the frame's entry in dict_ptrs (zd_plan.h
   // Sink::frame_dict); the used dictionaries' content addresses and, last, the address no-dictionary frames get
   uint64_t frame_dict, dict_ptrs;
+  // ZD_F_VERIFY_CHECKSUM plans only (0 elsewhere): u64 per frame, has << 32 | Content_Checksum (zd_plan.h
+  // Sink::frame_csum, among the descriptors); zd_k_verify's results, u64 digest and i8 ok per frame
+  uint64_t csum, vhash, vok;
   uint64_t total;
 };
 

@@ -131,6 +131,8 @@ struct zd_plan {
   int32_t dset_fallback = -1;
   uint32_t n_dict_comps = 0;            // prebuilt comps at the head of the plan (a dictionary plan: 0 or 1)
   std::vector<uint32_t> frame_dict;     // Sink::frame_dict of a plan that is not staged
+  std::vector<uint64_t> frame_csum;     // Sink::frame_csum of a ZD_F_VERIFY_CHECKSUM plan that is not staged
+  bool verify() const { return (flags & ZD_F_VERIFY_CHECKSUM) != 0; }
   bool with_dict() const { return dict != nullptr || dset != nullptr; }
   std::vector<HostPart> parts;          // the host walk's frames, in input order
   std::vector<size_t> part_f0;          // plan frame index of each part's first frame
@@ -150,6 +152,7 @@ struct zd_plan {
   // in the pinned staging until the upload: the vectors above stay empty)
   uint64_t n_comps = 0, n_blocks = 0, n_frames = 0, n_tables = 0, n_huf = 0, n_seq = 0, n_k4f = 0, n_copies = 0;
   uint64_t n_jframes = 0, n_jblk = 0, n_jseg = 0, n_k0only = 0;
+  uint64_t n_csums = 0;                         // zstd frames with a Content_Checksum (zd_k_verify's work)
   bool fused = false;                           // zd_k_fused plan (build_plan fuse_plan)
   bool last_fused = false;                      // the last zd_decode_async launched zd_k_fused
   std::vector<uint64_t> frame_out, frame_cap;   // output offset and capacity per frame
@@ -207,6 +210,7 @@ struct zd_plan {
   uint32_t dom_used = 0;                 // the groups (kDomNames) the last mode-2 launch recorded
   hipEvent_t dom_ev[2 * N_DOM] = {};
   hipEvent_t ev[N_KERNELS + 1] = {};
+  hipEvent_t ev_verify = nullptr;        // mode 1, a verified plan: after zd_k_verify (ev[N_KERNELS] is before it)
   bool ev_made = false;
   bool launched = false;
   hipStream_t last_stream = nullptr;     // the stream of the last zd_decode_async
@@ -453,11 +457,33 @@ void carve_tail(zd_plan* P, Workspace& W, const PlanCounts& T, uint64_t& o, uint
   W.redo = carve(std::max<uint64_t>(T.frames, 1));
   W.k2done = carve(4);
 }
+// A ZD_F_VERIFY_CHECKSUM plan's arrays: the stored checksums among the
+// descriptors the planner fills (after carve_head), zd_k_verify's results
+// among the device-only arrays (after carve_tail).  Other plans carve nothing.
+void carve_verify_head(const zd_plan* P, Workspace& W, const PlanCounts& T, uint64_t& o) {
+  if (!P->verify()) return;
+  W.csum = o; o = align_up(o + 8 * std::max<uint64_t>(T.frames, 1), 256);
+}
+void carve_verify_tail(const zd_plan* P, Workspace& W, const PlanCounts& T, uint64_t& o) {
+  if (!P->verify()) return;
+  W.vhash = o; o = align_up(o + 8 * std::max<uint64_t>(T.frames, 1), 256);
+  W.vok = o; o = align_up(o + std::max<uint64_t>(T.frames, 1), 256);
+}
+// zd_k_verify's results before any launch wrote them (and for a plan whose
+// frames carry no checksum, where it never runs): no digest, nothing checked
+int init_verify(zd_plan* P) {
+  if (!P->verify()) return 0;
+  const uint64_t n = std::max<uint64_t>(P->n_frames, 1);
+  HIPCHK(hipMemset(P->d_ws + P->W.vhash, 0, 8 * n));
+  HIPCHK(hipMemset(P->d_ws + P->W.vok, 0xFF, n));
+  return 0;
+}
 // The plan's array counts from the totals
 void plan_totals(zd_plan* P, const PlanCounts& T, bool fused) {
   P->n_comps = T.comps; P->n_blocks = T.blocks; P->n_frames = T.frames;
   P->n_tables = T.tables; P->n_huf = T.huf; P->n_seq = T.seq; P->n_k4f = T.k4f; P->n_copies = T.copies;
   P->n_jframes = T.jframes; P->n_jblk = T.jblk; P->n_jseg = T.jseg; P->n_k0only = T.k0only;
+  P->n_csums = T.csums;
   P->fused = plan_fused(fused, T.jframes, T.k4f);
 }
 void plan_info(zd_plan* P, const PlanCounts& T) {
@@ -581,6 +607,7 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
     W.frame_dict = o; o = align_up(o + 4 * std::max<uint64_t>(T.frames, 1), 256);
     W.dict_ptrs = o; o = align_up(o + 8 * (uint64_t)(X.ndset + 1), 256);
   }
+  carve_verify_head(P, W, T, o);
   P->desc_bytes = o;
   plan_totals(P, T, X.fused);
   P->frame_out.resize(T.frames);
@@ -613,7 +640,9 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
       for (uint32_t k = 0; k < X.ndset; k++) dp[k] = P->dset_used[k]->d_content;
       dp[X.ndset] = P->dset->d_none();
     }
+    if (P->verify()) S.frame_csum = (uint64_t*)(b + W.csum);
     P->frame_dict.clear();
+    P->frame_csum.clear();
     P->comps.clear(); P->blocks.clear(); P->fdesc.clear(); P->fstate0.clear();
     P->list_tables.clear(); P->list_huf.clear(); P->list_seq.clear(); P->list_k4f.clear(); P->copies.clear();
     P->jframes.clear(); P->jblkd.clear(); P->jsegd.clear();
@@ -635,6 +664,8 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
              P->jblkd.data(), P->jsegd.data(), nullptr, nullptr, nullptr};
     P->frame_dict.assign(X.dset ? T.frames : 0, 0);
     if (X.dset) S.frame_dict = P->frame_dict.data();
+    P->frame_csum.assign(P->verify() ? T.frames : 0, 0);
+    if (P->verify()) S.frame_csum = P->frame_csum.data();
   }
   S.frame_out = P->frame_out.data();
   S.frame_cap = P->frame_cap.data();
@@ -649,6 +680,7 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
   uint64_t j_maxseq = 0;
   for (const JMax& m : jm) j_maxseq = std::max(j_maxseq, m.m);
   carve_tail(P, W, T, o, T.jwords, T.jpieces, j_maxseq);
+  carve_verify_tail(P, W, T, o);
   W.total = o;
 
   plan_info(P, T);
@@ -770,6 +802,7 @@ int upload_desc(zd_plan* P) {
         {W.jblkd, P->jblkd.data(), P->jblkd.size() * sizeof(JBlkDesc)},
         {W.jsegd, P->jsegd.data(), P->jsegd.size() * sizeof(JSegDesc)},
         {W.frame_dict, P->frame_dict.data(), P->frame_dict.size() * 4},
+        {W.csum, P->frame_csum.data(), P->frame_csum.size() * 8},
     };
     for (const Piece& q : pieces)
       if (q.bytes) HIPCHK(hipMemcpy(P->d_ws + q.off, q.p, q.bytes, hipMemcpyHostToDevice));
@@ -780,7 +813,7 @@ int upload_desc(zd_plan* P) {
       HIPCHK(hipMemcpy(P->d_ws + W.dict_ptrs, dp.data(), dp.size() * 8, hipMemcpyHostToDevice));
     }
   }
-  return 0;
+  return init_verify(P);
 }
 
 int upload_plan(zd_plan* P) {
@@ -1274,9 +1307,11 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
     W.frame_dict = o; o = align_up(o + 4 * std::max<uint64_t>(T.frames, 1), 256);
     W.dict_ptrs = o; o = align_up(o + 8 * (uint64_t)(X.ndset + 1), 256);
   }
+  carve_verify_head(P, W, T, o);
   P->desc_bytes = o;
   plan_totals(P, T, X.fused);
   carve_tail(P, W, T, o, T.jwords, T.jpieces, shape.jmaxseq);
+  carve_verify_tail(P, W, T, o);
   W.hframes = o;
   o = align_up(o + sizeof(HostFrame) * std::max<uint64_t>(F, 1), 256);
   W.total = o;
@@ -1305,7 +1340,9 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
                (FrameState*)(b + W.frame_state0), (uint32_t*)(b + W.list_tables), (uint32_t*)(b + W.list_huf),
                (uint32_t*)(b + W.list_seq), (uint32_t*)(b + W.list_k4f), (CopyDesc*)(b + W.copies),
                (JFrame*)(b + W.jframes), (JBlkDesc*)(b + W.jblkd), (JSegDesc*)(b + W.jsegd), d_fout, d_fcap,
-               X.dset ? (uint32_t*)(b + W.frame_dict) : nullptr};
+               X.dset ? (uint32_t*)(b + W.frame_dict) : nullptr,
+               P->verify() ? (uint64_t*)(b + W.csum) : nullptr};
+  if (int r = init_verify(P)) return r;
   HIPCHK(launch_plan_fill(X, d_frames, d_blocks, F, B.d_cnt, B.d_tot, S, s));
   if (F) HIPCHK(hipMemcpyAsync(b + W.hframes, d_frames, F * sizeof(HostFrame), hipMemcpyDeviceToDevice, s));
   P->frame_out.resize(F);
@@ -1558,6 +1595,7 @@ const char* zd_status_name(int s) {
     case ZD_E_COMM: return "CommError";
     case ZD_E_DICT_CORRUPTED: return "DictionaryCorrupted";
     case ZD_E_DICT_MISMATCH: return "DictionaryMismatch";
+    case ZD_E_CHECKSUM_WRONG: return "ChecksumWrong";
     default: return "Unknown";
   }
 }
@@ -1730,6 +1768,7 @@ void zd_plan_destroy(zd_plan* P) {
   if (P->ev_made) {
     for (auto& e : P->ev) (void)hipEventDestroy(e);
     for (auto& e : P->dom_ev) (void)hipEventDestroy(e);
+    (void)hipEventDestroy(P->ev_verify);
   }
   aux_give(P);
   delete P;
@@ -1753,6 +1792,7 @@ int zd_plan_set_profiling(zd_plan* P, int enable) {
   if (enable && !P->ev_made) {
     for (auto& e : P->ev) HIPCHK(hipEventCreate(&e));
     for (auto& e : P->dom_ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventCreate(&P->ev_verify));
     P->ev_made = true;
   }
   P->profile = enable == 1;
@@ -1783,6 +1823,15 @@ int zd_plan_kernel_times(zd_plan* P, const char** names, float* ms, int cap, int
     float t = 0;
     HIPCHK(hipEventElapsedTime(&t, P->ev[k], P->ev[k + 1]));
     if (ms) ms[k] = t;
+  }
+  // a verified plan's last launch, after the pipeline's
+  if (k == N_KERNELS && k < cap && P->verify() && P->n_csums) {
+    HIPCHK(hipEventSynchronize(P->ev_verify));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, P->ev[N_KERNELS], P->ev_verify));
+    if (names) names[k] = "zd_k_verify";
+    if (ms) ms[k] = t;
+    k++;
   }
   if (n) *n = k;
   return ZD_OK;
@@ -1845,6 +1894,13 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
     HIPCHK(hipMemsetAsync(P->d_ws + P->W.k2done, 0, 4, s));
   }
   HIPCHK(launch_pipeline(a));
+  // ZD_F_VERIFY_CHECKSUM: the frames' digests against their stored checksums,
+  // behind everything the pipeline queued (its second stream has joined `s`)
+  // and before whatever reads the frame states next (zd_k_batch_results)
+  if (P->verify() && P->n_csums) {
+    HIPCHK(launch_verify(P->d_ws, P->W, out, (uint32_t)P->n_frames, P->cus, s));
+    if (R.profiling == 1) HIPCHK(hipEventRecord(P->ev_verify, s));
+  }
   P->launched = true;
   P->last_stream = s;
   return ZD_OK;
@@ -2856,6 +2912,14 @@ int zd_batch_device_results(const zd_batch* B, const int32_t** d_status, const u
   return ZD_OK;
 }
 
+int zd_batch_device_checksums(const zd_batch* B, const uint64_t** d_hash, const int8_t** d_ok) {
+  if (!B || !(B->flags & ZD_F_VERIFY_CHECKSUM)) return ZD_E_INVALID_ARG;
+  const zd_plan* P = B->P;               // (null: a batch of no chunks, arrays of no entries)
+  if (d_hash) *d_hash = P ? (const uint64_t*)(P->d_ws + P->W.vhash) : nullptr;
+  if (d_ok) *d_ok = P ? (const int8_t*)(P->d_ws + P->W.vok) : nullptr;
+  return ZD_OK;
+}
+
 int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, size_t cap, uint64_t* nfailed) {
   if (!B || ((status || len) && cap < B->n)) return ZD_E_INVALID_ARG;
   if (nfailed) *nfailed = 0;
@@ -2905,6 +2969,18 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
       std::vector<uint64_t> ln2(m);
       r = zd_batch_decode_async(Q, s);
       if (!r) r = zd_batch_results(Q, s, st2.data(), ln2.data(), m, nullptr);
+      // (the internal batch keeps ZD_F_VERIFY_CHECKSUM: its chunks' digests too)
+      if (!r && P->verify() && Q->P)
+        for (size_t k = 0; k < m && !r; k++) {
+          const size_t i = redo[k];
+          if (hipMemcpy(P->d_ws + P->W.vhash + 8 * i, Q->P->d_ws + Q->P->W.vhash + 8 * k, 8,
+                        hipMemcpyDeviceToDevice) != hipSuccess ||
+              hipMemcpy(P->d_ws + P->W.vok + i, Q->P->d_ws + Q->P->W.vok + k, 1, hipMemcpyDeviceToDevice) !=
+                  hipSuccess) {
+            (void)hipGetLastError();
+            r = ZD_E_HIP;
+          }
+        }
       zd_batch_destroy(Q);
       if (r) return r;
       for (size_t k = 0; k < m; k++) {

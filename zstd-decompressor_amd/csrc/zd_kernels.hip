@@ -5711,6 +5711,171 @@ hipError_t launch_xxh64(const uint8_t* base, const uint64_t* d_off, const uint64
 }
 
 // ---------------------------------------------------------------------------
+// zd_k_verify: Content_Checksums enforced inside the decode launch
+// (ZD_F_VERIFY_CHECKSUM; the last launch of decode_launch).  zd_k_xxh64's
+// layout -- XXH64 over one frame is four serial chains, one per accumulator,
+// so four lanes a frame and 16 frames a wave -- over the plan's own frame
+// states: a zstd frame with a stored checksum (csum[f] = has << 32 | word)
+// whose key is KEY_NONE is hashed where the route left it, out +
+// FrameDesc::out for FrameState::out_len bytes; every other frame is skipped
+// unread (digest 0, ok -1).  A mismatch writes the frame's key, which is
+// KEY_NONE then: no atomic, the pipeline is over and nothing else writes it.
+//
+// How the bytes reach the lanes: the quad fetches one 128-byte line (four
+// stripes) as whole 32-byte rows, lane j the two 16-byte halves of stripe j
+// (half the load instructions and cache-line visits of 8-byte loads 32 bytes
+// apart), then a 4 x 4 transpose of 64-bit words inside the quad (two DPP
+// quad_perm exchanges) leaves lane k with word k of the four stripes, its
+// accumulator's input.  VF_U lines are loaded a trip, the next trip's before
+// this trip's rounds, so 2 x VF_U x 2 KiB a wave are in flight: plans of few
+// frames run one wave a SIMD or less, and what hides HBM latency there is the
+// depth of one wave's loads.  The stripes past the last whole line are
+// 8-byte loads, the tail below 32 bytes is read bytewise by lane 0
+// (xx_finish).  Every load lies inside [p, p + len): exactly the frame's
+// bytes at whatever alignment the destination has (16-byte loads of
+// alignment 1, as ldg16 everywhere).
+// LINES = false: zd_k_xxh64's loop as the body, 8-byte loads 32 bytes apart
+// and no transpose.  Plans of VF_WORDS_WAVES_PER_CU waves a CU or more take
+// it: there occupancy covers the latency, the two bodies measured the same
+// (65,536 x 4 KiB: 0.056-0.062 ms either way) and the transposes are VALU
+// work the chains could use; below it the rows win 2.1 x (8,192 x 128 KiB,
+// one 100 MB frame; EXPERIMENTS.md).  ZD_VERIFY_WORDS (experiment builds):
+// that body always.
+// ---------------------------------------------------------------------------
+#ifndef ZD_VERIFY_LINES
+#define ZD_VERIFY_LINES 4
+#endif
+constexpr int VF_U = ZD_VERIFY_LINES;
+constexpr uint32_t VF_WORDS_WAVES_PER_CU = 16;   // four waves a SIMD
+template <int CTRL>
+__device__ inline uint64_t qdpp64(uint64_t x) {
+  return (uint64_t)qdpp<CTRL>((uint32_t)x) | ((uint64_t)qdpp<CTRL>((uint32_t)(x >> 32)) << 32);
+}
+// Lane j of a quad holds row j of a 4 x 4 matrix of 64-bit words on entry and
+// column j on return: 2 x 2 blocks exchanged with the lane one away, then with
+// the lane two away (each lane sends the word its partner keeps a place for).
+__device__ inline void quad_transpose64(uint64_t w[4], int sub) {
+  const bool b0 = (sub & 1) != 0, b1 = (sub & 2) != 0;
+#pragma unroll
+  for (int p = 0; p < 4; p += 2) {
+    const uint64_t r = qdpp64<QP_SWAP1>(b0 ? w[p] : w[p + 1]);
+    w[p] = b0 ? r : w[p];
+    w[p + 1] = b0 ? w[p + 1] : r;
+  }
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const uint64_t r = qdpp64<QP_SWAP2>(b1 ? w[p] : w[p + 2]);
+    w[p] = b1 ? r : w[p];
+    w[p + 2] = b1 ? w[p + 2] : r;
+  }
+}
+template <bool LINES>
+__global__ __launch_bounds__(64) void zd_k_verify(const uint8_t* __restrict__ out, const FrameDesc* __restrict__ frames,
+                                                  FrameState* fstate, const uint64_t* __restrict__ csum, uint32_t n,
+                                                  uint64_t* vhash, int8_t* vok) {
+  const int lane = threadIdx.x, sub = lane & 3;
+  const uint32_t f = blockIdx.x * 16 + (lane >> 2);
+  uint64_t cs = 0, L = 0;
+  const uint8_t* p = out;
+  uint32_t nblocks = 0;
+  bool act = false;
+  if (f < n) {
+    cs = csum[f];
+    act = (cs >> 32) != 0 && fstate[f].key == KEY_NONE;
+    if (act) {
+      const FrameDesc fd = frames[f];
+      L = fstate[f].out_len;
+      p = out + fd.out;
+      nblocks = fd.nblocks;
+    }
+  }
+  const uint64_t nst = L / 32;
+  uint64_t v = xx_acc_init(sub);
+  uint64_t s = 0;
+  if (LINES) {
+  const uint64_t nl = nst / 4;
+  auto row = [&](uint64_t line, u32x4& a, u32x4& b) {
+    const uint8_t* q = p + 128 * line + 32 * sub;
+    a = ldg16(q);
+    b = ldg16(q + 16);
+  };
+  auto eat = [&](const u32x4& a, const u32x4& b) {
+    uint64_t w[4] = {(uint64_t)a.x | ((uint64_t)a.y << 32), (uint64_t)a.z | ((uint64_t)a.w << 32),
+                     (uint64_t)b.x | ((uint64_t)b.y << 32), (uint64_t)b.z | ((uint64_t)b.w << 32)};
+    quad_transpose64(w, sub);
+    v = xx_round(xx_round(xx_round(xx_round(v, w[0]), w[1]), w[2]), w[3]);
+  };
+  u32x4 ca[VF_U] = {}, cb[VF_U] = {};
+  uint64_t t = 0;
+  if (VF_U <= nl) {
+#pragma unroll
+    for (int k = 0; k < VF_U; k++) row(k, ca[k], cb[k]);
+  }
+  while (t + VF_U <= nl) {
+    u32x4 na[VF_U], nb[VF_U];
+#pragma unroll
+    for (int k = 0; k < VF_U; k++) { na[k] = ca[k]; nb[k] = cb[k]; }
+    if (t + 2 * VF_U <= nl) {                       // the next trip's lines, before this trip's rounds
+#pragma unroll
+      for (int k = 0; k < VF_U; k++) row(t + VF_U + k, na[k], nb[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < VF_U; k++) eat(ca[k], cb[k]);
+#pragma unroll
+    for (int k = 0; k < VF_U; k++) { ca[k] = na[k]; cb[k] = nb[k]; }
+    t += VF_U;
+  }
+  for (; t < nl; t++) {
+    u32x4 a, b;
+    row(t, a, b);
+    eat(a, b);
+  }
+  s = 4 * nl;
+  } else {
+  for (; s + 4 <= nst; s += 4) {                  // four stripes per trip, loads first
+    const uint64_t w0 = *(g_cu64a1*)(p + 32 * s + 8 * sub), w1 = *(g_cu64a1*)(p + 32 * (s + 1) + 8 * sub);
+    const uint64_t w2 = *(g_cu64a1*)(p + 32 * (s + 2) + 8 * sub), w3 = *(g_cu64a1*)(p + 32 * (s + 3) + 8 * sub);
+    v = xx_round(xx_round(xx_round(xx_round(v, w0), w1), w2), w3);
+  }
+  }
+  for (; s < nst; s++) v = xx_round(v, *(g_cu64a1*)(p + 32 * s + 8 * sub));
+  // (the lanes have reconverged: the four accumulators into every lane of the quad)
+  const uint64_t acc[4] = {qdpp64<0x00>(v), qdpp64<0x55>(v), qdpp64<0xAA>(v), qdpp64<0xFF>(v)};
+  if (f < n && sub == 0) {
+    uint64_t h = 0;
+    int8_t ok = -1;
+    if (act) {
+      h = xx_finish(L, acc, p + 32 * nst, (uint32_t)(L - 32 * nst));
+      ok = (uint32_t)h == (uint32_t)cs ? 1 : 0;
+      if (!ok) fstate[f].key = make_key(PH_DECODE, nblocks, DS_CHECKSUM, 0, ZD_E_CHECKSUM_WRONG);
+    }
+    vhash[f] = h;
+    vok[f] = ok;
+  }
+}
+
+hipError_t launch_verify(uint8_t* ws, const Workspace& W, const uint8_t* out, uint32_t n_frames, uint32_t cus,
+                         hipStream_t s) {
+  if (!n_frames) return hipSuccess;
+  const uint32_t waves = (n_frames + 15) / 16;
+#ifndef ZD_VERIFY_WORDS
+  const bool lines = waves < VF_WORDS_WAVES_PER_CU * (uint64_t)cus;
+#else
+  const bool lines = false;
+#endif
+  auto* frames = (const FrameDesc*)(ws + W.frames);
+  auto* fstate = (FrameState*)(ws + W.frame_state);
+  auto* csum = (const uint64_t*)(ws + W.csum);
+  auto* vhash = (uint64_t*)(ws + W.vhash);
+  auto* vok = (int8_t*)(ws + W.vok);
+  if (lines)
+    hipLaunchKernelGGL(zd_k_verify<true>, dim3(waves), dim3(64), 0, s, out, frames, fstate, csum, n_frames, vhash, vok);
+  else
+    hipLaunchKernelGGL(zd_k_verify<false>, dim3(waves), dim3(64), 0, s, out, frames, fstate, csum, n_frames, vhash, vok);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // compaction (frames without an exact FCS layout)
 // ---------------------------------------------------------------------------
 // One frame per blockIdx.x, COMPACT_SPLIT workgroups (blockIdx.y) over

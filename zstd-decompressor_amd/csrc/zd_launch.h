@@ -68,6 +68,15 @@ hipError_t launch_compact(const uint8_t* staging, uint8_t* dst, const uint64_t* 
 hipError_t launch_xxh64(const uint8_t* base, const uint64_t* d_off, const uint64_t* d_len, uint32_t n,
                         uint64_t* d_hash, hipStream_t s);
 
+// zd_k_verify (a ZD_F_VERIFY_CHECKSUM plan, the last launch of decode_launch):
+// every zstd frame that carries a Content_Checksum (W.csum) and whose key is
+// KEY_NONE is hashed where the route left it, out + FrameDesc::out for
+// FrameState::out_len bytes; digest and ok go to W.vhash / W.vok, and a
+// mismatch writes the frame's key (DS_CHECKSUM, ZD_E_CHECKSUM_WRONG).
+// cus: the device's compute units (the load pattern follows the waves a CU gets).
+hipError_t launch_verify(uint8_t* ws, const Workspace& W, const uint8_t* out, uint32_t n_frames, uint32_t cus,
+                         hipStream_t s);
+
 // Device header walk (zd_walk.h): ranges [first + k chunk, + chunk) of src[0, n),
 // count pass (fill = false: WalkRange summaries) or fill pass (frames/blocks at
 // the summaries' f_off / b_off).

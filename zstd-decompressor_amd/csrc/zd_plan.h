@@ -43,15 +43,16 @@ struct PlanCounts {
   uint64_t jwords = 0;           // K4J state words: a frame's region starts a 16-word piece, 16 words of slack after
   uint64_t jpieces = 0;          // K4J 16-byte pieces over the frames' regions
   uint64_t k0only = 0;           // frames K0 copies whole (every block raw / RLE): no K4 for them
+  uint64_t csums = 0;            // zstd frames that carry a Content_Checksum (zd_k_verify runs when there is one)
   ZD_HD bool exact() const { return inexact == 0; }
   ZD_HD void add(const PlanCounts& o) {
     frames += o.frames; blocks += o.blocks; comps += o.comps; luts += o.luts; fses += o.fses; lits += o.lits;
     nrec += o.nrec; nseq += o.nseq; out += o.out; tables += o.tables; huf += o.huf; seq += o.seq; k4f += o.k4f;
     copies += o.copies; jframes += o.jframes; jblk += o.jblk; jseg += o.jseg; inexact += o.inexact;
-    jwords += o.jwords; jpieces += o.jpieces; k0only += o.k0only;
+    jwords += o.jwords; jpieces += o.jpieces; k0only += o.k0only; csums += o.csums;
   }
 };
-constexpr int PLAN_FIELDS = 21;
+constexpr int PLAN_FIELDS = 22;
 static_assert(sizeof(PlanCounts) == PLAN_FIELDS * 8, "PlanCounts: u64 fields only");
 
 // One dictionary of a dictionary-set plan (zd_plan_create_dicts), as the
@@ -128,6 +129,7 @@ struct Sink {
   JSegDesc* jsegd;
   uint64_t *frame_out, *frame_cap;
   uint32_t* frame_dict;    // a dictionary-set plan: the frame's entry in the plan's table (PlanCtx::dset), else null
+  uint64_t* frame_csum;    // a ZD_F_VERIFY_CHECKSUM plan: has << 32 | the frame's Content_Checksum, else null
 };
 
 // One frame's descriptors at the running indices c (build_plan).  FILL: the
@@ -378,6 +380,10 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
       c.k0only++;
     }
   }
+  // the stored Content_Checksum, for zd_k_verify (a frame that failed to index has none to check)
+  const bool has_csum = hf.d.kind == ZD_FRAME_ZSTD && hf.d.has_checksum && !frame_failed_host;
+  if (has_csum) c.csums++;
+  if (FILL && S.frame_csum) S.frame_csum[fi] = has_csum ? (1ull << 32) | hf.d.checksum : 0;
   if (FILL) {
     S.frame_out[fi] = out;
     S.frame_cap[fi] = cap;

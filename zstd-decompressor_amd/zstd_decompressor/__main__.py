@@ -1,6 +1,6 @@
 """Command line, mirroring the reference CLI (src/main.rs:7-60):
 
-    python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]...
+    python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]... [--verify]
 
 Decodes every frame of FILE on the GPU (the HIP pipeline behind zd_decompress)
 and writes the concatenated output to stdout or --output.  As in the
@@ -11,6 +11,9 @@ exit status 101).  --info prints one line per frame instead (the reference
 prints the parsed frames with `{:#x?}`).  Extra, beyond the reference:
 --check-checksums verifies Content_Checksum (XXH64) on the GPU and reports
 mismatches on stderr (the reference computes and never enforces it);
+--verify enforces it inside the decode launch: a frame whose bytes do not hash
+to its Content_Checksum ends the run with `Error: frame N: ChecksumWrong`
+(exit status 1), as `zstd -d` fails such a file;
 -D DICT decodes every frame with the dictionary file DICT (formatted or raw
 content), as zstd's own -D does; -D given several times makes a dictionary
 set: every frame decodes with the dictionary its Dictionary_ID names, a frame
@@ -54,6 +57,9 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("-p", "--print-skippable", action="store_true", help="Output Skippable frames as well")
     ap.add_argument("--check-checksums", action="store_true",
                     help="verify Content_Checksum (XXH64) on the GPU; mismatches go to stderr (not in the reference)")
+    ap.add_argument("--verify", action="store_true",
+                    help="fail a frame whose decoded bytes do not match its Content_Checksum, as zstd -d does "
+                         "(not in the reference)")
     ap.add_argument("-D", dest="dictionary", metavar="dict", action="append",
                     help="decode with this dictionary file, as zstd -D; repeat it for a set of dictionaries, "
                          "each frame choosing by its Dictionary_ID (not in the reference)")
@@ -81,7 +87,7 @@ def main(argv=None) -> int:
     except _lib.ZdError as e:
         print(f"Error: dictionary: {e.name}", file=sys.stderr)
         return 1
-    plan = Plan(data, a.print_skippable, dictionary=dictionary)
+    plan = Plan(data, a.print_skippable, _lib.F_VERIFY_CHECKSUM if a.verify else 0, dictionary=dictionary)
     dev = torch.device("cuda", torch.cuda.current_device())
     d_src = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
     if data:

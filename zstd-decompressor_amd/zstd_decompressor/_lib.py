@@ -111,6 +111,7 @@ SIGNATURES = {
     "zd_batch_info_get": (C.c_int, [_vp, C.POINTER(BatchInfo)]),
     "zd_batch_decode_async": (C.c_int, [_vp, _vp]),
     "zd_batch_device_results": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "zd_batch_device_checksums": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "zd_batch_results": (C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _sz,
                                    C.POINTER(C.c_uint64)]),
     "zd_batch_checksums": (C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
@@ -240,6 +241,7 @@ RESERVED_BLOCK_TYPE = -50
 UNRECOGNIZED_MAGIC, FRAME_RESERVED_SET, MISSING_CHECKSUM, WINDOW_SIZE_TOO_BIG = -60, -61, -64, -66
 REF_PANIC, OUT_OF_DOMAIN, DST_TOO_SMALL, INVALID_ARG, HIP, NO_MEMORY, NOT_DECODED = -90, -91, -92, -93, -94, -95, -96
 DICT_CORRUPTED, DICT_MISMATCH = -98, -99
+CHECKSUM_WRONG = -100  # F_VERIFY_CHECKSUM: the frame decoded, its bytes do not hash to its Content_Checksum
 DICT_SET_MAX = 4096    # ZD_DICT_SET_MAX
 F_SKIPPABLE = 1
 F_BLOCK_PARALLEL = 2   # every frame with a compressed block -> K4J (block-parallel execute)
@@ -250,5 +252,6 @@ F_K1_LANES = 64        # K1's sequence half on serial lanes in plans of <= 16,38
 F_J_ONE_ROUND = 128    # test switch: K4J pointer jumping cut to one round of one hop
 F_SEQ_NO_LATENCY = 256 # K3Q instead of the one-block-per-wave K3L in plans of few blocks
 F_K1_SPLIT = 512       # K1 as a parse pass and a build pass in a plan of any size
+F_VERIFY_CHECKSUM = 1024  # Content_Checksums verified inside the decode launch (zd_k_verify): CHECKSUM_WRONG
 SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)

@@ -125,10 +125,13 @@ def _decompress(data: bytes, flags: int, dictionary=None):
         plan.close()
 
 
-def decompress(data: bytes, print_skippable: bool = False, dictionary=None) -> bytes:
+def decompress(data: bytes, print_skippable: bool = False, dictionary=None, verify: bool = False) -> bytes:
     """Decode every frame of `data` on the GPU (host in, host out);
-    dictionary: a Dictionary every frame decodes with, or a DictionarySet."""
-    st, out = _decompress(data, _lib.F_SKIPPABLE if print_skippable else 0, dictionary)
+    dictionary: a Dictionary every frame decodes with, or a DictionarySet;
+    verify: a frame whose bytes do not hash to its Content_Checksum raises
+    ZdError(CHECKSUM_WRONG), as libzstd fails such a frame."""
+    flags = (_lib.F_SKIPPABLE if print_skippable else 0) | (_lib.F_VERIFY_CHECKSUM if verify else 0)
+    st, out = _decompress(data, flags, dictionary)
     _lib.check(st, "zd_decompress")
     return out
 
@@ -479,6 +482,16 @@ class Batch:
         st, ln = C.c_void_p(), C.c_void_p()
         _lib.check(_lib.lib().zd_batch_device_results(self._h, C.byref(st), C.byref(ln)), "zd_batch_device_results")
         return st.value or 0, ln.value or 0
+
+    def device_checksums(self):
+        """(device address of the uint64 XXH64 digests, device address of the
+        int8 ok values: 1 match / 0 mismatch / -1 none or not decoded) of a
+        batch made with _lib.F_VERIFY_CHECKSUM: written by the verification
+        pass decode_async queues before the result arrays."""
+        h, ok = C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.lib().zd_batch_device_checksums(self._h, C.byref(h), C.byref(ok)),
+                   "zd_batch_device_checksums")
+        return h.value or 0, ok.value or 0
 
     def results(self, stream: int = 0):
         """(statuses, lengths) per chunk, after waiting for `stream`."""
