@@ -38,6 +38,13 @@ def lib():
         # (the parameter API with a dictionary: a Content_Checksum, no Frame_Content_Size)
         L.ZSTD_CCtx_loadDictionary.restype = C.c_size_t
         L.ZSTD_CCtx_loadDictionary.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        # (a prefix: raw content for one frame, ZSTD_dct_rawContent)
+        L.ZSTD_CCtx_refPrefix.restype = C.c_size_t
+        L.ZSTD_CCtx_refPrefix.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.ZSTD_DCtx_refPrefix.restype = C.c_size_t
+        L.ZSTD_DCtx_refPrefix.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.ZSTD_decompressDCtx.restype = C.c_size_t
+        L.ZSTD_decompressDCtx.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         _bound = True
     return L
 
@@ -93,6 +100,39 @@ def decompress(frame: bytes, dictionary: bytes, size: int) -> bytes:
     dctx = L.ZSTD_createDCtx()
     try:
         n = libzstd._chk(L.ZSTD_decompress_usingDict(dctx, dst, size, frame, len(frame), dictionary, len(dictionary)))
+    finally:
+        L.ZSTD_freeDCtx(dctx)
+    return dst.raw[:n]
+
+
+def prefix_compress(data: bytes, prefix: bytes, level: int = 3, checksum: bool = False,
+                    content_size: bool = True) -> bytes:
+    """One frame compressed against `prefix` as raw content, whatever its first
+    bytes (ZSTD_CCtx_refPrefix + ZSTD_compress2: what `zstd --patch-from` does)."""
+    L = lib()
+    cap = L.ZSTD_compressBound(len(data))
+    dst = C.create_string_buffer(cap)
+    cctx = L.ZSTD_createCCtx()
+    try:
+        libzstd._chk(L.ZSTD_CCtx_setParameter(cctx, libzstd.ZSTD_c_compressionLevel, level))
+        libzstd._chk(L.ZSTD_CCtx_setParameter(cctx, libzstd.ZSTD_c_checksumFlag, int(checksum)))
+        libzstd._chk(L.ZSTD_CCtx_setParameter(cctx, libzstd.ZSTD_c_contentSizeFlag, int(content_size)))
+        libzstd._chk(L.ZSTD_CCtx_refPrefix(cctx, prefix, len(prefix)))
+        n = libzstd._chk(L.ZSTD_compress2(cctx, dst, cap, data, len(data)))
+    finally:
+        L.ZSTD_freeCCtx(cctx)
+    return dst.raw[:n]
+
+
+def prefix_decompress(frame: bytes, prefix: bytes, size: int) -> bytes:
+    """ZSTD_DCtx_refPrefix + ZSTD_decompressDCtx of one frame into `size`
+    bytes at most; raises RuntimeError with libzstd's message on failure."""
+    L = lib()
+    dst = C.create_string_buffer(max(size, 1))
+    dctx = L.ZSTD_createDCtx()
+    try:
+        libzstd._chk(L.ZSTD_DCtx_refPrefix(dctx, prefix, len(prefix)))
+        n = libzstd._chk(L.ZSTD_decompressDCtx(dctx, dst, size, frame, len(frame)))
     finally:
         L.ZSTD_freeDCtx(dctx)
     return dst.raw[:n]

@@ -506,6 +506,8 @@ typedef struct zd_batch_info {
    *               (zd_k_batch_fit) are queued here and waited for in host_ns
    *   host_ns     the device planner's launches (zd_k_plan_*) and their waits
    *   upload_ns   workspace allocation, dictionary tables and small uploads */
+  uint64_t prefix_bytes_total; /* a prefix batch: the sum of prefix_bytes[i] over the chunks that
+                                * kept their prefix (0 for any other batch) */
 } zd_batch_info;
 
 /* A batch over nchunks chunks: chunk i is the src_bytes[i] bytes at device
@@ -590,6 +592,75 @@ int  zd_batch_create_device(const void* const* d_src_ptrs, const uint64_t* d_src
 int  zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes,
                                   void* const* d_dst_ptrs, const uint64_t* d_dst_cap, size_t nchunks,
                                   uint32_t flags, const zd_dict_set* set, void* stream, zd_batch** out);
+/* Deltas: a batch whose chunk i decodes against its own PREFIX, the
+ * prefix_bytes[i] bytes at device address d_prefix[i] -- what
+ * ZSTD_DCtx_refPrefix gives one frame and `zstd --patch-from` one file, for
+ * every chunk of a batch at once.  The six arrays are host arrays of nchunks
+ * entries; the first four are zd_batch_create's.
+ *  - Prefix content.  A prefix is raw content, always (ZSTD_dct_rawContent, as
+ *    refPrefix): a leading dictionary magic (37 a4 30 ec) is just bytes.
+ *  - Decode model.  Chunk i's frame starts at position prefix_bytes[i]; its
+ *    first repeat offsets are 1, 4, 8 and it has no previous tables.  A match
+ *    may reach any prefix byte, however far the frame has advanced (no window
+ *    check, as everywhere here); an offset larger than the prefix size plus the
+ *    position is ZD_E_IMPOSSIBLE_VALUE.  The output holds the frame's own bytes
+ *    only.
+ *  - No prefix.  prefix_bytes[i] == 0 (d_prefix[i] may then be NULL): the chunk
+ *    decodes with no prefix, exactly as in a plain batch -- but for the
+ *    batch-wide relaxation every dictionary batch has: an empty Raw literals
+ *    section is accepted.
+ *  - Dictionary_ID.  A frame that names a non-zero Dictionary_ID is
+ *    ZD_E_DICT_MISMATCH, for that chunk alone.
+ *  - Everything else zd_batch_create says about a chunk holds unchanged: one
+ *    zstd frame per chunk with skippable frames skipped, a status of its own for
+ *    every chunk, length 0 on failure, nothing written outside [d_dst[i],
+ *    d_dst[i] + dst_cap[i]).
+ *  - Executors.  The streaming executor only, like dictionary batches:
+ *    zd_batch_info.executors is 0 and ZD_F_BLOCK_PARALLEL is ignored.  A chunk
+ *    whose prefix size plus capacity passes the executor's int32 positions
+ *    (0x7FFF0000) is ZD_E_OUT_OF_DOMAIN, alone, whether or not its frame has
+ *    sequences.  Frames keep the reference's 8 MiB window limit, so a
+ *    --patch-from archive made with --long beyond 8 MiB is refused, as in any
+ *    plan here.
+ *  - Read bounds.  No byte outside [d_prefix[i], d_prefix[i] + prefix_bytes[i])
+ *    is ever read through a prefix pointer, at any alignment: the caller owes
+ *    no padding on either side.
+ *  - When prefixes are read.  By zd_batch_decode_async, not here: addresses and
+ *    sizes are fixed at creation, the CONTENTS may change between launches (not
+ *    during one), and the buffers must stay valid until zd_batch_destroy.  The
+ *    sources are gathered at creation, as in zd_batch_create.
+ *  - Overlap.  Prefixes may overlap one another and the sources.  A prefix range
+ *    that overlaps any destination range of the batch is ZD_E_INVALID_ARG.
+ *  - Flags.  ZD_F_VERIFY_CHECKSUM works and hashes the frame's own bytes;
+ *    ZD_F_SKIPPABLE is ZD_E_INVALID_ARG.
+ *  - A prefix batch takes no dictionary and no dictionary set.
+ * The result is an ordinary batch: every zd_batch_* call works on it;
+ * zd_batch_info.prefix_bytes_total is the prefixes' bytes in all.
+ * ZD_E_INVALID_ARG, before any HIP call: what zd_batch_create refuses; a NULL
+ * d_prefix or prefix_bytes with nchunks > 0; a NULL d_prefix[i] with
+ * prefix_bytes[i] > 0; a prefix range that wraps; a prefix range that overlaps
+ * a destination range.  nchunks == 0 is ZD_OK.
+ * Limits (not in this interface): no packed prefix batches; prefixes cannot be
+ * re-pointed after creation; a chunk's prefix cannot be another chunk's output
+ * of the SAME launch (chunks run concurrently); no prefixes on the LDS-resident,
+ * block-parallel or fused executors; none in zd_plan_*, the sharded calls or
+ * zd_context. */
+int  zd_batch_create_prefix(const void* const* d_src, const uint64_t* src_bytes,
+                            void* const* d_dst, const uint64_t* dst_cap,
+                            const void* const* d_prefix, const uint64_t* prefix_bytes,
+                            size_t nchunks, uint32_t flags, void* stream, zd_batch** out);
+/* zd_batch_create_prefix for a chunk table on the device: the six arrays are
+ * DEVICE arrays of nchunks entries, under zd_batch_create_device's terms (the
+ * batch keeps its own copies; device_built = 1).  The per-entry cases are a
+ * per-chunk outcome: a NULL d_prefix[i] with prefix_bytes[i] > 0 or a prefix
+ * range that wraps makes that chunk ZD_E_INVALID_ARG (length 0), and nothing of
+ * the chunk or its prefix is read.  A prefix range that overlaps a destination
+ * range is NOT checked: keeping them apart is the caller's duty, as for the
+ * destinations themselves. */
+int  zd_batch_create_device_prefix(const void* const* d_src_ptrs, const uint64_t* d_src_bytes,
+                                   void* const* d_dst_ptrs, const uint64_t* d_dst_cap,
+                                   const void* const* d_prefix_ptrs, const uint64_t* d_prefix_bytes,
+                                   size_t nchunks, uint32_t flags, void* stream, zd_batch** out);
 /* What chunks need of their destinations, asked on the device: chunk i is the
  * d_src_bytes[i] bytes at d_src_ptrs[i], as in zd_batch_create_device.  All
  * five arrays are DEVICE arrays of nchunks entries; d_status and d_exact may be
@@ -685,7 +756,18 @@ int  zd_batch_output_layout(const zd_batch* batch, uint64_t* out_bytes,
  * zd_batch_decode_async on a packed batch with out_bytes > 0 and no binding is
  * ZD_E_INVALID_ARG. */
 int  zd_batch_bind_output(zd_batch* batch, void* d_out, uint64_t cap);
+/* The batch's figures.  zd_batch_info grew by prefix_bytes_total without a new
+ * ZD_ABI_VERSION, so the exported zd_batch_info_get keeps writing the 80 bytes
+ * up to and including upload_ns -- a caller built against the earlier header
+ * passes no more -- and zd_batch_info_get_sized writes the first info_bytes
+ * bytes of the current struct (at most all of it; fewer than 80 is
+ * ZD_E_INVALID_ARG).  C and C++ code that includes this header gets the sized
+ * call under the old name, so its whole struct is filled. */
 int  zd_batch_info_get(const zd_batch* batch, zd_batch_info* info);
+int  zd_batch_info_get_sized(const zd_batch* batch, zd_batch_info* info, size_t info_bytes);
+#ifndef ZD_NO_SIZED_INFO_MACRO
+#define zd_batch_info_get(batch, info) zd_batch_info_get_sized((batch), (info), sizeof(zd_batch_info))
+#endif
 /* Launches the decode of every chunk on `stream`, ending with a kernel that
  * writes the batch's device result arrays (zd_batch_device_results).  No
  * allocation, no host synchronisation, like zd_decode_async; may be called

@@ -490,6 +490,7 @@ struct Workspace {
   uint64_t hframes;                                     // device-built plans: the walk's frame index (zd_walk.h HostFrame)
   // dictionary-set plans only (0 elsewhere): u32 per frame, the frame's entry in dict_ptrs (zd_plan.h
   // Sink::frame_dict); the used dictionaries' content addresses and, last, the address no-dictionary frames get
+  // (a prefix batch: dict_ptrs alone, frame f's prefix address at entry f, 0 for a frame without one)
   uint64_t frame_dict, dict_ptrs;
   // ZD_F_VERIFY_CHECKSUM plans only (0 elsewhere): u64 per frame, has << 32 | Content_Checksum (zd_plan.h
   // Sink::frame_csum, among the descriptors); zd_k_verify's results, u64 digest and i8 ok per frame

@@ -133,7 +133,14 @@ struct zd_plan {
   std::vector<uint32_t> frame_dict;     // Sink::frame_dict of a plan that is not staged
   std::vector<uint64_t> frame_csum;     // Sink::frame_csum of a ZD_F_VERIFY_CHECKSUM plan that is not staged
   bool verify() const { return (flags & ZD_F_VERIFY_CHECKSUM) != 0; }
-  bool with_dict() const { return dict != nullptr || dset != nullptr; }
+  // a prefix batch (zd_batch_create_prefix; never with `dict` or `dset`): frame
+  // f's own raw-content prefix, prefix_bytes[f] bytes at the caller's address
+  // prefix_ptrs[f] (host vectors; a batch made from device arrays leaves them
+  // empty and has d_prefix_ptrs / d_prefix_bytes, the batch's own copies)
+  bool prefix = false;
+  std::vector<uint64_t> prefix_ptrs, prefix_bytes;
+  const uint64_t *d_prefix_ptrs = nullptr, *d_prefix_bytes = nullptr;
+  bool with_dict() const { return dict != nullptr || dset != nullptr || prefix; }
   std::vector<HostPart> parts;          // the host walk's frames, in input order
   std::vector<size_t> part_f0;          // plan frame index of each part's first frame
   size_t nframes = 0;
@@ -383,6 +390,7 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   }
   X.place_out = P->place_out.empty() ? nullptr : P->place_out.data();
   X.place_cap = P->place_out.empty() ? nullptr : P->place_cap.data();
+  if (P->prefix) X.prefix_bytes = P->d_prefix_bytes ? P->d_prefix_bytes : P->prefix_bytes.data();
   RouteIn in{};
   in.cus = P->cus;
   in.nframes = P->nframes;
@@ -607,6 +615,7 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
     W.frame_dict = o; o = align_up(o + 4 * std::max<uint64_t>(T.frames, 1), 256);
     W.dict_ptrs = o; o = align_up(o + 8 * (uint64_t)(X.ndset + 1), 256);
   }
+  if (P->prefix) { W.dict_ptrs = o; o = align_up(o + 8 * std::max<uint64_t>(T.frames, 1), 256); }
   carve_verify_head(P, W, T, o);
   P->desc_bytes = o;
   plan_totals(P, T, X.fused);
@@ -640,6 +649,8 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
       for (uint32_t k = 0; k < X.ndset; k++) dp[k] = P->dset_used[k]->d_content;
       dp[X.ndset] = P->dset->d_none();
     }
+    if (P->prefix && !P->prefix_ptrs.empty())
+      memcpy(b + W.dict_ptrs, P->prefix_ptrs.data(), 8 * P->prefix_ptrs.size());
     if (P->verify()) S.frame_csum = (uint64_t*)(b + W.csum);
     P->frame_dict.clear();
     P->frame_csum.clear();
@@ -812,6 +823,8 @@ int upload_desc(zd_plan* P) {
       dp.push_back(P->dset->d_none());
       HIPCHK(hipMemcpy(P->d_ws + W.dict_ptrs, dp.data(), dp.size() * 8, hipMemcpyHostToDevice));
     }
+    if (P->prefix && !P->prefix_ptrs.empty())
+      HIPCHK(hipMemcpy(P->d_ws + W.dict_ptrs, P->prefix_ptrs.data(), 8 * P->prefix_ptrs.size(), hipMemcpyHostToDevice));
   }
   return init_verify(P);
 }
@@ -1307,6 +1320,7 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
     W.frame_dict = o; o = align_up(o + 4 * std::max<uint64_t>(T.frames, 1), 256);
     W.dict_ptrs = o; o = align_up(o + 8 * (uint64_t)(X.ndset + 1), 256);
   }
+  if (P->prefix) { W.dict_ptrs = o; o = align_up(o + 8 * std::max<uint64_t>(T.frames, 1), 256); }
   carve_verify_head(P, W, T, o);
   P->desc_bytes = o;
   plan_totals(P, T, X.fused);
@@ -1330,6 +1344,11 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
     for (const DictData* d : P->dset_used) dp.push_back(d->d_content);
     dp.push_back(P->dset->d_none());
     HIPCHK(hipMemcpy(b + W.dict_ptrs, dp.data(), dp.size() * 8, hipMemcpyHostToDevice));
+  }
+  // (a prefix batch: the checked addresses, from the batch's own array)
+  if (P->prefix && F) {
+    if (!P->d_prefix_ptrs) return ZD_E_INVALID_ARG;
+    HIPCHK(hipMemcpyAsync(b + W.dict_ptrs, P->d_prefix_ptrs, 8 * F, hipMemcpyDeviceToDevice, s));
   }
   if (in)
     in->alloc_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - ta)
@@ -1880,7 +1899,7 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
   // the route, resolved every launch (profiling may have been switched since
   // the last one); the rest of `a` is what the route's launches need
   const LaunchIn in{P->cus, P->n_frames, P->n_tables, P->n_huf, P->n_seq, P->flags, P->fused,
-                    P->dset ? K4_DICT_SET : P->dict ? K4_DICT : K4_PLAIN, P->profile ? 1 : P->profile_dom ? 2 : 0};
+                    P->prefix ? K4_PREFIX : P->dset ? K4_DICT_SET : P->dict ? K4_DICT : K4_PLAIN, P->profile ? 1 : P->profile_dom ? 2 : 0};
   const LaunchRoute R = a.route = launch_route(in, route_env());
   // (every plan has its second stream, aux_take, and a profiled one its events, zd_plan_set_profiling)
   if (((R.fork || R.k1_fork) && !P->aux) || (R.profiling && !P->ev_made)) return ZD_E_HIP;
@@ -2418,6 +2437,10 @@ struct zd_batch {
   // layout, outbase the bound buffer (zd_batch_bind_output; null until then)
   bool packed = false;
   uint64_t out_bytes = 0;
+  // a prefix batch (zd_batch_create_prefix / _device_prefix); made from device
+  // arrays: the checked prefix addresses and sizes, in d_arr
+  bool prefix = false;
+  uint64_t *d_pfx = nullptr, *d_pfx_bytes = nullptr;
   int host_arrays() {
     if (!device_built || goff.size() == n) return 0;
     std::vector<uint64_t> o(n), z(n), d(n), c(n);
@@ -2450,13 +2473,17 @@ void zd_batch_destroy(zd_batch* B) {
   delete B;
 }
 
-// zd_batch_create / zd_batch_create_dicts: one dictionary, a set, or neither
+// zd_batch_create / zd_batch_create_dicts / zd_batch_create_prefix: one
+// dictionary, a set, a prefix per chunk (`with_prefix`; d_prefix / prefix_bytes
+// host arrays), or none of them
 static int batch_create(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
                         const uint64_t* dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
-                        const zd_dict_set* set, void* stream, zd_batch** out) {
+                        const zd_dict_set* set, void* stream, zd_batch** out, bool with_prefix = false,
+                        const void* const* d_prefix = nullptr, const uint64_t* prefix_bytes = nullptr) {
   // ---- argument checks: no HIP call before they are done ----
   if (!out || (flags & ZD_F_SKIPPABLE)) return ZD_E_INVALID_ARG;
   if (nchunks && (!d_src || !src_bytes || !d_dst || !dst_cap)) return ZD_E_INVALID_ARG;
+  if (with_prefix && (dict || set || (nchunks && (!d_prefix || !prefix_bytes)))) return ZD_E_INVALID_ARG;
   if (nchunks >= (1ull << 31) || (dict && !dict->p) || (set && !set->p)) return ZD_E_INVALID_ARG;
   const size_t n = nchunks;
   {
@@ -2471,6 +2498,16 @@ static int batch_create(const void* const* d_src, const uint64_t* src_bytes, voi
     std::sort(ranges.begin(), ranges.end());
     for (size_t k = 1; k < ranges.size(); k++)
       if (ranges[k].first < ranges[k - 1].first + ranges[k - 1].second) return ZD_E_INVALID_ARG;
+    // a prefix is read while the destinations are written: no prefix range may
+    // meet one (the sorted destinations are disjoint, so of those that start
+    // below the prefix's end the last one reaches furthest)
+    for (size_t i = 0; with_prefix && i < n; i++) {
+      const uint64_t a = (uint64_t)(uintptr_t)d_prefix[i], z = prefix_bytes[i];
+      if ((!a && z) || a + z < a) return ZD_E_INVALID_ARG;
+      if (!z) continue;
+      auto it = std::lower_bound(ranges.begin(), ranges.end(), std::pair<uint64_t, uint64_t>{a + z, 0});
+      if (it != ranges.begin() && (it - 1)->first + (it - 1)->second > a) return ZD_E_INVALID_ARG;
+    }
   }
   zd_batch* B = new (std::nothrow) zd_batch();
   if (!B) return ZD_E_NO_MEMORY;
@@ -2479,6 +2516,7 @@ static int batch_create(const void* const* d_src, const uint64_t* src_bytes, voi
   B->n = n;
   B->flags = flags;
   B->info.nchunks = n;
+  B->prefix = with_prefix;
   if (!n) { *out = hold.release(); return ZD_OK; }
 
   HIPCHK(hipGetDevice(&B->dev));
@@ -2554,6 +2592,15 @@ static int batch_create(const void* const* d_src, const uint64_t* src_bytes, voi
   P->flags = flags;
   P->dict = B->dict;
   P->dset = B->dset;
+  if (with_prefix) {
+    P->prefix = true;
+    P->prefix_ptrs.resize(n);
+    P->prefix_bytes.assign(prefix_bytes, prefix_bytes + n);
+    for (size_t i = 0; i < n; i++) {
+      P->prefix_ptrs[i] = prefix_bytes[i] ? (uint64_t)(uintptr_t)d_prefix[i] : 0;
+      B->info.prefix_bytes_total += prefix_bytes[i];
+    }
+  }
   const bool rfc_empty_lits = P->with_dict();
   std::vector<uint8_t> bind(n, 0);
   P->place_out.assign(head.begin() + 3 * (long)n, head.begin() + 4 * (long)n);
@@ -2650,6 +2697,13 @@ int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* c
   return batch_create(d_src, src_bytes, d_dst, dst_cap, nchunks, flags, dict, nullptr, stream, out);
 }
 
+int zd_batch_create_prefix(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
+                           const uint64_t* dst_cap, const void* const* d_prefix, const uint64_t* prefix_bytes,
+                           size_t nchunks, uint32_t flags, void* stream, zd_batch** out) {
+  return batch_create(d_src, src_bytes, d_dst, dst_cap, nchunks, flags, nullptr, nullptr, stream, out, true, d_prefix,
+                      prefix_bytes);
+}
+
 int zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
                           const uint64_t* dst_cap, size_t nchunks, uint32_t flags, const zd_dict_set* set, void* stream,
                           zd_batch** out) {
@@ -2668,10 +2722,13 @@ int zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes, v
 // pass and the planner run on those.
 static int batch_create_device(const void* const* d_src, const uint64_t* d_src_bytes, void* const* d_dst,
                                const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
-                               const zd_dict_set* set, void* stream, zd_batch** out, uint32_t align = 0) {
+                               const zd_dict_set* set, void* stream, zd_batch** out, uint32_t align = 0,
+                               bool with_prefix = false, const void* const* d_prefix = nullptr,
+                               const uint64_t* d_prefix_bytes = nullptr) {
   // ---- argument checks: no HIP call before they are done ----
   const bool packed = align != 0;
   if (!out || (flags & ZD_F_SKIPPABLE)) return ZD_E_INVALID_ARG;
+  if (with_prefix && (dict || set || packed || (nchunks && (!d_prefix || !d_prefix_bytes)))) return ZD_E_INVALID_ARG;
   if (nchunks && (!d_src || !d_src_bytes || (!packed && (!d_dst || !d_dst_cap)))) return ZD_E_INVALID_ARG;
   if (nchunks >= (1ull << 31) || (dict && !dict->p) || (set && !set->p)) return ZD_E_INVALID_ARG;
   const size_t n = nchunks;
@@ -2683,6 +2740,7 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
   B->flags = flags;
   B->device_built = true;
   B->packed = packed;
+  B->prefix = with_prefix;
   B->info.nchunks = n;
   B->info.device_built = 1;
   if (!n) { *out = hold.release(); return ZD_OK; }
@@ -2706,8 +2764,11 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
   const uint64_t nt = (n + 255) / 256;
   const uint64_t scratch_words = 2 * (nt + 1) + 1, res_words = 4;
   const uint64_t bytes_at = 9 * 8 * n + 2 * 4 * n, words_at = align_up(bytes_at + 2 * n, 8);
-  B->arr_bytes = words_at + 8 * (scratch_words + res_words);
+  // (a prefix batch: the prefixes' addresses and sizes after everything else)
+  const uint64_t pfx_at = words_at + 8 * (scratch_words + res_words);
+  B->arr_bytes = pfx_at + (with_prefix ? 2 * 8 * n : 0);
   HIPCHK(hipMalloc(&B->d_arr, B->arr_bytes));
+  if (with_prefix) { B->d_pfx = (uint64_t*)(B->d_arr + pfx_at); B->d_pfx_bytes = B->d_pfx + n; }
   uint64_t* a = (uint64_t*)B->d_arr;
   B->d_src = a; B->d_size = a + n; B->d_off = a + 2 * n; B->d_piece0 = a + 3 * n; B->d_out = a + 4 * n;
   B->d_cap = a + 5 * n; B->d_boff = a + 6 * n; B->d_len = a + 7 * n; B->d_hash = a + 8 * n;
@@ -2730,12 +2791,13 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
   if (!WB.h_small && hipHostMalloc((void**)&WB.h_small, 64 * 8, hipHostMallocDefault) != hipSuccess) return ZD_E_HIP;
 
   // ---- layout: the entries' checks, the gathered offsets, the pieces, the lowest destination ----
-  const BatchArrays A{B->d_src, B->d_size, B->d_off, B->d_piece0, B->d_out, B->d_cap, B->d_flag};
+  const BatchArrays A{B->d_src, B->d_size, B->d_off, B->d_piece0, B->d_out, B->d_cap, B->d_flag, B->d_pfx, B->d_pfx_bytes};
   HIPCHK(launch_batch_layout((const uint64_t*)d_src, d_src_bytes, (const uint64_t*)d_dst, d_dst_cap, (uint32_t)n, A,
-                             d_scratch, d_res, s));
-  HIPCHK(hipMemcpyAsync(WB.h_small, d_res, 3 * 8, hipMemcpyDeviceToHost, s));
+                             d_scratch, d_res, s, with_prefix ? (const uint64_t*)d_prefix : nullptr, d_prefix_bytes));
+  HIPCHK(hipMemcpyAsync(WB.h_small, d_res, 4 * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   const uint64_t total = WB.h_small[0], npieces = WB.h_small[1];
+  if (with_prefix) B->info.prefix_bytes_total = WB.h_small[3];
   B->outbase = (uint8_t*)(uintptr_t)WB.h_small[2];
   if (npieces * (COPY_PIECE / 4096) >= (1ull << 31)) return ZD_E_OUT_OF_DOMAIN;   // zd_k_gather's grid
   HIPCHK(ws_alloc(B->dev, std::max<uint64_t>(total, 16), &B->d_gather, &B->gather_alloc));
@@ -2751,6 +2813,7 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
   P->flags = flags;
   P->dict = B->dict;
   P->dset = B->dset;
+  if (with_prefix) { P->prefix = true; P->d_prefix_ptrs = B->d_pfx; P->d_prefix_bytes = B->d_pfx_bytes; }
   const bool rfc_empty_lits = P->with_dict();
   HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, nullptr, nullptr, nullptr, false, s));
   HIPCHK(launch_scan64(B->d_boff, B->d_nblk, n, 1, n, d_scratch, s));
@@ -2831,6 +2894,14 @@ int zd_batch_create_device(const void* const* d_src_ptrs, const uint64_t* d_src_
   return batch_create_device(d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, nchunks, flags, dict, nullptr, stream, out);
 }
 
+int zd_batch_create_device_prefix(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
+                                  const uint64_t* d_dst_cap, const void* const* d_prefix_ptrs,
+                                  const uint64_t* d_prefix_bytes, size_t nchunks, uint32_t flags, void* stream,
+                                  zd_batch** out) {
+  return batch_create_device(d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, nchunks, flags, nullptr, nullptr, stream,
+                             out, 0, true, d_prefix_ptrs, d_prefix_bytes);
+}
+
 int zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
                                  const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict_set* set,
                                  void* stream, zd_batch** out) {
@@ -2883,9 +2954,15 @@ int zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_b
   return ZD_OK;
 }
 
+// (the exported symbol: the struct as it was before prefix_bytes_total, see include/zd.h)
+#undef zd_batch_info_get
 int zd_batch_info_get(const zd_batch* B, zd_batch_info* info) {
-  if (!B || !info) return ZD_E_INVALID_ARG;
-  *info = B->info;
+  return zd_batch_info_get_sized(B, info, offsetof(zd_batch_info, prefix_bytes_total));
+}
+
+int zd_batch_info_get_sized(const zd_batch* B, zd_batch_info* info, size_t info_bytes) {
+  if (!B || !info || info_bytes < offsetof(zd_batch_info, prefix_bytes_total)) return ZD_E_INVALID_ARG;
+  memcpy(info, &B->info, std::min(info_bytes, sizeof(zd_batch_info)));
   return ZD_OK;
 }
 

@@ -2719,13 +2719,17 @@ __device__ inline void k4_sync() {
 // DICT (zd_k_execute_dict): the positions [0, lo) before the frame are the
 // dictionary's content (dict[p]), the frame's own bytes start at lo and `out`
 // is moved down by lo, so out + p is the byte's address for every p >= lo.
-template <int C_, int W_, int B_, bool DICT_ = false>
+// DICT_ 1: the content lies in a buffer of the library's, 16 readable bytes on
+// both sides of it; 2 (zd_k_execute_prefix): in the caller's, and no byte
+// outside dict[0, lo) is read (lo may be 0 and dict null then).
+template <int C_, int W_, int B_, int DICT_ = 0>
 struct K4W {
   static constexpr int C = C_, W = W_, B = B_;
-  static constexpr bool DICT = DICT_;
+  static constexpr bool DICT = DICT_ != 0;
+  static constexpr bool EXACT = DICT_ == 2;
   l_u8* buf;
   uint8_t* out;            // frame output (frame position 0)
-  const uint8_t* dict;     // DICT: dictionary content (frame position 0), 16 readable bytes on both sides
+  const uint8_t* dict;     // DICT: dictionary content (frame position 0), 16 readable bytes on both sides (not EXACT)
   int32_t lo;              // DICT: frame position of the frame's first own byte (the content size)
   int32_t a0;              // frame position of the first 16-byte aligned HBM address (0..15)
   int32_t hs;              // frame position of buf[0]; hs = a0 (mod 16), may be < 0
@@ -2977,7 +2981,9 @@ __device__ inline bool k4f_wait_recs(const K4Fuse& z, uint32_t rec_end) {
   return false;
 }
 
-template <bool FZ, bool DICT = false>
+// DICT: 0 none, 1 a dictionary or dictionary set (dict, or dict_ptrs[frame_dict[f]]),
+// 2 a prefix batch (dict_ptrs[f], the caller's buffer, read with exact bounds)
+template <bool FZ, int DICT = 0>
 __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __restrict__ src, uint8_t* outbase,
                                                    const FrameDesc* __restrict__ frames, FrameState* fstate,
                                                    const BlockRec* __restrict__ blocks,
@@ -3032,13 +3038,14 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
   // positions below F.out_len0 the dictionary; the planner keeps the sum
   // below K4_MAX_FRAME_OUT)
   const uint64_t cap64 = DICT ? F.out_cap + F.out_len0 : F.out_cap;
-  if constexpr (DICT) {
+  if constexpr (DICT != 0) {
     // (a dictionary-set plan: the frame's own dictionary, read beside its
     // descriptor -- f is the wave's, so both loads are scalar and the pointer
     // stays wave-uniform; a frame without a dictionary has lo = 0 and an
     // address that is readable 16 bytes either side, which only the window
     // preload below touches)
-    X.dict = dict_ptrs ? dict_ptrs[frame_dict[f]] : dict;
+    if constexpr (DICT == 2) X.dict = dict_ptrs[f];
+    else X.dict = dict_ptrs ? dict_ptrs[frame_dict[f]] : dict;
     X.lo = (int32_t)F.out_len0;
     X.out -= F.out_len0;
   }
@@ -3051,7 +3058,20 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
     // window start: aligned, at most K4_W bytes back (context API: the
     // existing output's tail comes back from HBM)
     X.hs = X.alignd(X.pos > K4_W ? X.pos - K4_W : 0);
-    if constexpr (DICT) {
+    if constexpr (DICT == 2) {
+      // the prefix's tail: the pieces inside [0, lo) whole, the (at most two)
+      // edge pieces byte by byte from the positions inside it -- nothing when
+      // lo = 0, so a null pointer is never read; then K0's bytes
+      for (int32_t p = X.hs + 16 * lane; p < X.lo; p += 1024) {
+        if (p >= 0 && p + 16 <= X.lo) {
+          *(l_u32x4a1*)X.at(p) = ldg16_src(X.dict + p);
+        } else {
+          const int32_t e = p + 16 < X.lo ? p + 16 : X.lo;
+          for (int32_t b = p > 0 ? p : 0; b < e; b++) *X.at(b) = X.dict[b];
+        }
+      }
+      for (int32_t p = (X.hs > X.lo ? X.hs : X.lo) + lane; p < X.pos; p += 64) *X.at(p) = X.out[p];
+    } else if constexpr (DICT != 0) {
       // the dictionary's tail in 16-byte pieces (hs >= -15 and the last piece
       // ends below lo + 16: the buffer's padding), then K0's bytes
       for (int32_t p = X.hs + 16 * lane; p < X.lo; p += 1024) *(l_u32x4a1*)X.at(p) = ldg16_src(X.dict + p);
@@ -3316,8 +3336,10 @@ __device__ __attribute__((always_inline)) inline void k4_body(const uint8_t* __r
         // from the frame's output; a source that spans both goes to the
         // frontier rounds (src16 merges the two there)
         const uint8_t* fsrc = X.out;
-        if constexpr (DICT) {
-          const bool ind = shi <= X.lo;
+        if constexpr (DICT != 0) {
+          // (a prefix: every load of the lane ends at or below max(shi, slo + 16),
+          // which must not pass lo -- else the frontier rounds, like a spanning lane)
+          const bool ind = shi <= X.lo && (DICT != 2 || slo + 16 <= X.lo);
           far0 = far0 && (ind || slo - 16 >= X.lo);
           fsrc = ind ? X.dict : (const uint8_t*)X.out;
         }
@@ -3618,8 +3640,8 @@ __global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute_dict(const uint8_
   __shared__ __attribute__((aligned(16))) uint8_t stg[K4_STG + 16];
   __shared__ uint32_t codelut[2 * 64];
   const K4Lds M{(l_u8*)win + K4_WPAD, (l_u8*)pat, (l_u8*)stab, (l_u8*)stg, (l_u32*)codelut};
-  k4_body<false, true>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x,
-                       f_end, gridDim.x, nullptr, M, nullptr, nullptr, dict);
+  k4_body<false, 1>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x,
+                    f_end, gridDim.x, nullptr, M, nullptr, nullptr, dict);
 }
 
 // The streaming K4 of a dictionary-set plan (zd_plan_create_dicts): the same
@@ -3642,8 +3664,33 @@ __global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute_dicts(const uint8
   __shared__ __attribute__((aligned(16))) uint8_t stg[K4_STG + 16];
   __shared__ uint32_t codelut[2 * 64];
   const K4Lds M{(l_u8*)win + K4_WPAD, (l_u8*)pat, (l_u8*)stab, (l_u8*)stg, (l_u32*)codelut};
-  k4_body<false, true>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x,
-                       f_end, gridDim.x, nullptr, M, nullptr, nullptr, nullptr, dict_ptrs, frame_dict);
+  k4_body<false, 1>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x,
+                    f_end, gridDim.x, nullptr, M, nullptr, nullptr, nullptr, dict_ptrs, frame_dict);
+}
+
+// The streaming K4 of a prefix batch (zd_batch_create_prefix): the same body,
+// frame f's positions [0, F.out_len0) the caller's buffer prefix_ptrs[f] (any
+// alignment, no padding owed, null when the size is 0), read where it lies and
+// never outside it (k4_body DICT 2: the window preload's edge pieces bytewise,
+// pass 0's far loads only when they end inside it, src16 / byte_before as for
+// a dictionary).
+__global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute_prefix(const uint8_t* __restrict__ src, uint8_t* outbase,
+                                                   const FrameDesc* __restrict__ frames, FrameState* fstate,
+                                                   const BlockRec* __restrict__ blocks,
+                                                   const CompBlock* __restrict__ comp,
+                                                   const CompState* __restrict__ cstate,
+                                                   const uint8_t* __restrict__ lits,
+                                                   const uint64_t* __restrict__ seqs,
+                                                   const uint16_t* __restrict__ fses, uint32_t f_begin,
+                                                   uint32_t f_end, const uint8_t* const* __restrict__ prefix_ptrs) {
+  __shared__ __attribute__((aligned(16))) uint8_t win[K4_WPAD + K4_C];
+  __shared__ __attribute__((aligned(16))) uint8_t pat[64];
+  __shared__ __attribute__((aligned(16))) uint8_t stab[3 * FSE_TAB];
+  __shared__ __attribute__((aligned(16))) uint8_t stg[K4_STG + 16];
+  __shared__ uint32_t codelut[2 * 64];
+  const K4Lds M{(l_u8*)win + K4_WPAD, (l_u8*)pat, (l_u8*)stab, (l_u8*)stg, (l_u32*)codelut};
+  k4_body<false, 2>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f_begin + blockIdx.x,
+                    f_end, gridDim.x, nullptr, M, nullptr, nullptr, nullptr, prefix_ptrs);
 }
 
 // ---------------------------------------------------------------------------
@@ -6037,7 +6084,11 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     if (n && k4_work) {  // frames on the streaming K4 (K4F's, K4J's and K0's exit at once)
       const bool tm = !redo && k4_work;
       if (tm) if ((e = dom(DOM_K4, 0)) != hipSuccess) return e;
-      if (R.k4 == K4_DICT_SET)                 // each frame's own dictionary
+      if (R.k4 == K4_PREFIX)                   // each frame's own prefix, in the caller's buffer
+        hipLaunchKernelGGL(zd_k_execute_prefix, dim3(n), dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp,
+                           (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
+                           (const uint16_t*)fses, f0, f1, (const uint8_t* const*)(ws + W.dict_ptrs));
+      else if (R.k4 == K4_DICT_SET)            // each frame's own dictionary
         hipLaunchKernelGGL(zd_k_execute_dicts, dim3(n), dim3(64), 0, st, a.src, a.out, frames, fstate, blocks, comp,
                            (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
                            (const uint16_t*)fses, f0, f1, (const uint8_t* const*)(ws + W.dict_ptrs),
@@ -6630,16 +6681,26 @@ __global__ __launch_bounds__(256) void zd_k_batch_layout(const uint64_t* __restr
                                                          const uint64_t* __restrict__ size,
                                                          const uint64_t* __restrict__ dst,
                                                          const uint64_t* __restrict__ cap, uint32_t n, BatchArrays A,
-                                                         unsigned long long* lowest) {
+                                                         unsigned long long* lowest,
+                                                         const uint64_t* __restrict__ pfx,
+                                                         const uint64_t* __restrict__ pfx_bytes,
+                                                         unsigned long long* pfx_total) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  unsigned long long low = ~0ull;
+  unsigned long long low = ~0ull, psum = 0;
   if (i < n) {
     // (a packed batch has no destination arrays: its places come from zd_k_batch_pack)
     uint64_t s = src[i], z = size[i], d = dst ? dst[i] : 0, c = cap ? cap[i] : 0;
+    // (a prefix batch, zd_batch_create_device_prefix: the chunk's prefix entry is checked with the rest)
+    uint64_t p = pfx ? pfx[i] : 0, pz = pfx ? pfx_bytes[i] : 0;
     uint8_t flag = CHUNK_OK;
-    if ((!s && z) || (!d && c) || s + z < s || d + c < d) flag = CHUNK_INVALID;
+    if ((!s && z) || (!d && c) || s + z < s || d + c < d || (!p && pz) || p + pz < p) flag = CHUNK_INVALID;
     else if (z >= (1ull << 32)) flag = CHUNK_TOO_LARGE;
-    if (flag) s = z = d = c = 0;
+    if (flag) s = z = d = c = p = pz = 0;
+    if (pfx) {
+      A.pfx[i] = pz ? p : 0;
+      A.pfx_bytes[i] = pz;
+      psum = pz;
+    }
     A.src[i] = s;
     A.size[i] = z;
     A.off[i] = ((z + 15) & ~15ull) + ZD_SRC_PADDING;
@@ -6655,6 +6716,10 @@ __global__ __launch_bounds__(256) void zd_k_batch_layout(const uint64_t* __restr
     low = o < low ? o : low;
   }
   if ((threadIdx.x & 63) == 0 && low != ~0ull) atomicMin(lowest, low);
+  if (pfx) {
+    for (int k = 32; k; k >>= 1) psum += __shfl_xor(psum, k);
+    if ((threadIdx.x & 63) == 0 && psum) atomicAdd(pfx_total, psum);
+  }
 }
 
 // Exclusive scans over n entries of `ncols` u64 arrays (column c at a + c *
@@ -6840,13 +6905,17 @@ hipError_t launch_scan64(uint64_t* a, const uint32_t* in32, uint64_t n, uint32_t
 }
 
 hipError_t launch_batch_layout(const uint64_t* src, const uint64_t* size, const uint64_t* dst, const uint64_t* cap,
-                               uint32_t n, const BatchArrays& A, uint64_t* scratch, uint64_t* res, hipStream_t s) {
+                               uint32_t n, const BatchArrays& A, uint64_t* scratch, uint64_t* res, hipStream_t s,
+                               const uint64_t* pfx, const uint64_t* pfx_bytes) {
   if (!n || A.piece0 != A.off + n) return hipErrorInvalidValue;   // (off | piece0: the two scanned columns)
+  if (pfx && (!pfx_bytes || !A.pfx || !A.pfx_bytes)) return hipErrorInvalidValue;
   const uint32_t nt = (n + 255) / 256;
   unsigned long long* lowest = (unsigned long long*)(scratch + 2 * ((uint64_t)nt + 1));
   hipError_t e = hipMemsetAsync(lowest, 0xFF, 8, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(zd_k_batch_layout, dim3(nt), dim3(256), 0, s, src, size, dst, cap, n, A, lowest);
+  if (pfx && (e = hipMemsetAsync(res + 3, 0, 8, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(zd_k_batch_layout, dim3(nt), dim3(256), 0, s, src, size, dst, cap, n, A, lowest, pfx, pfx_bytes,
+                     (unsigned long long*)(res + 3));
   e = launch_scan64(A.off, nullptr, n, 2, n, scratch, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(zd_k_batch_place, dim3(nt), dim3(256), 0, s, A.out, n, (const unsigned long long*)lowest,

@@ -35,7 +35,8 @@ struct LaunchArgs {
   // route.k4 == K4_DICT (zd_plan_create_dict): the dictionary's content on the
   // device (frame positions [0, FrameDesc::out_len0)).  A dictionary-set plan
   // (K4_DICT_SET) takes each frame's from the workspace's table
-  // (Workspace::dict_ptrs, ::frame_dict)
+  // (Workspace::dict_ptrs, ::frame_dict), a prefix batch (K4_PREFIX) frame f's
+  // prefix from dict_ptrs[f]
   const uint8_t* dict = nullptr;
 };
 
@@ -132,13 +133,21 @@ struct BatchArrays {
   uint64_t* out;           // the destination's offset from the lowest destination
   uint64_t* cap;           // the caller's capacity (0 for a refused chunk)
   uint8_t* flag;           // CHUNK_*
+  // a prefix batch (zd_batch_create_device_prefix; null otherwise): the chunk's
+  // prefix address and size, 0 / 0 for a refused chunk or an empty prefix
+  uint64_t* pfx = nullptr;
+  uint64_t* pfx_bytes = nullptr;
 };
 enum : uint8_t { CHUNK_OK = 0, CHUNK_INVALID = 1, CHUNK_TOO_LARGE = 2 };
 // zd_k_batch_layout, the scans of off / piece0, zd_k_batch_place.  scratch: 2 *
 // (tiles + 1) + 1 words (tiles of 256 chunks); res[0..3): gathered bytes,
-// pieces, the lowest destination.
+// pieces, the lowest destination.  pfx / pfx_bytes (a prefix batch): the
+// caller's prefix entries, checked with the rest (a NULL address with a size,
+// a range that wraps: CHUNK_INVALID) and copied to A.pfx / A.pfx_bytes; res[3]:
+// the prefixes' bytes in all.
 hipError_t launch_batch_layout(const uint64_t* src, const uint64_t* size, const uint64_t* dst, const uint64_t* cap,
-                               uint32_t n, const BatchArrays& A, uint64_t* scratch, uint64_t* res, hipStream_t s);
+                               uint32_t n, const BatchArrays& A, uint64_t* scratch, uint64_t* res, hipStream_t s,
+                               const uint64_t* pfx = nullptr, const uint64_t* pfx_bytes = nullptr);
 // Exclusive scan of n entries of ncols u64 arrays in place (column c at a + c *
 // stride; in32: one column's input instead); tot: ncols x (tiles + 1) words,
 // a column's total last.

@@ -103,6 +103,13 @@ struct PlanCtx {
   const PlanDict* dset;
   uint32_t ndset;
   int32_t dset_fallback;
+  // Optional per-frame prefix sizes (a prefix batch, zd_batch_create_prefix:
+  // host array; zd_batch_create_device_prefix: device array; null everywhere
+  // else; `dict` is set with it, never `dset`): frame fi decodes against its own
+  // raw-content prefix of prefix_bytes[fi] bytes (0: none) -- out_len0 is that
+  // size, the first repeat offsets are 1, 4, 8, there are no previous tables,
+  // and a frame that names a Dictionary_ID is ZD_E_DICT_MISMATCH.
+  const uint64_t* prefix_bytes;
 };
 
 // The entry of Dictionary_ID id (non-zero) in a table sorted by ID, or -1.
@@ -171,6 +178,12 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
       huf_prev = tab_prev[0] = tab_prev[1] = tab_prev[2] = d.comp;
     }
     if (FILL) S.frame_dict[fi] = e >= 0 ? (uint32_t)e : X.ndset;
+  } else if (X.prefix_bytes) {
+    // the frame's own prefix: raw content, so no ID fits it
+    if (names_dict) fs.key = plan_min(fs.key, make_key(PH_PARSE, 0, PS_STRUCT, 0, ZD_E_DICT_MISMATCH));
+    out_len0 = X.prefix_bytes[fi];
+    fs.rep[0] = 1; fs.rep[1] = 4; fs.rep[2] = 8;
+    huf_prev = tab_prev[0] = tab_prev[1] = tab_prev[2] = -1;
   } else if (X.dict && names_dict && hf.d.dict_id != X.dict_id) {
     // a frame that names another dictionary stops the plan like a frame that
     // failed to index (no block of it is planned to run)
@@ -292,6 +305,15 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   if (X.place_out) {
     out = X.place_out[fi];
     cap = plan_min(cap, X.place_cap[fi]);
+  }
+  // a prefix the streaming K4's int32 positions cannot hold (with the frame's
+  // capacity, sequences or not: the frame starts at the prefix's size): no
+  // block of the frame runs, and a size past the limit itself is not even kept
+  // (K4 truncates out_len0 to 32 bits)
+  if (X.prefix_bytes && out_len0 && (out_len0 > K4_MAX_FRAME_OUT || cap + out_len0 > K4_MAX_FRAME_OUT)) {
+    fs.key = plan_min(fs.key, make_key(PH_LIMIT, 0, 0, 0, ZD_E_OUT_OF_DOMAIN));
+    fd.nblocks = 0;
+    if (out_len0 > K4_MAX_FRAME_OUT) fd.out_len0 = out_len0 = 0;
   }
   fd.out = out;
   fd.out_cap = cap;

@@ -1,6 +1,7 @@
 """Command line, mirroring the reference CLI (src/main.rs:7-60):
 
     python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]... [--verify]
+    python -m zstd_decompressor FILE --patch-from OLD -o FILE
 
 Decodes every frame of FILE on the GPU (the HIP pipeline behind zd_decompress)
 and writes the concatenated output to stdout or --output.  As in the
@@ -18,6 +19,11 @@ to its Content_Checksum ends the run with `Error: frame N: ChecksumWrong`
 content), as zstd's own -D does; -D given several times makes a dictionary
 set: every frame decodes with the dictionary its Dictionary_ID names, a frame
 without an ID with the one raw-content file if there is one, else the first.
+--patch-from OLD decodes FILE, one frame made by `zstd --patch-from OLD`,
+against the bytes of OLD as its prefix (raw content, whatever they start
+with): a prefix batch of one chunk with OLD uploaded.  The output is written
+as bytes (a patched file need not be text); a failure prints the chunk's
+status name and exits with status 1.  Not together with -D.
 """
 from __future__ import annotations
 
@@ -25,7 +31,7 @@ import argparse
 import sys
 
 from . import _lib
-from .batch import Dictionary, DictionarySet, Plan, frames_index
+from .batch import Dictionary, DictionarySet, Plan, decode_tensors, frames_index
 
 
 def _info(data: bytes) -> int:
@@ -63,7 +69,40 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("-D", dest="dictionary", metavar="dict", action="append",
                     help="decode with this dictionary file, as zstd -D; repeat it for a set of dictionaries, "
                          "each frame choosing by its Dictionary_ID (not in the reference)")
+    ap.add_argument("--patch-from", dest="patch_from", metavar="old",
+                    help="decode the one frame of the input against this file as its prefix, as zstd --patch-from "
+                         "(not in the reference; not together with -D)")
     return ap
+
+
+def _patch(a, data: bytes) -> int:
+    """FILE against OLD: one chunk of a prefix batch, sized by the frame's own
+    Frame_Content_Size, else by 128 KiB per block (what a batch reserves)."""
+    import torch
+    old = open(a.patch_from, "rb").read()
+    frames, blocks, st, _ = frames_index(data)
+    cap = 0
+    for f in frames:
+        if f["kind"] == 1:
+            continue
+        cs = f["content_size"]
+        cap = max(cap, cs if cs != (1 << 64) - 1 else (128 << 10) * max(f["num_blocks"], 1))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) if b else torch.empty(0, dtype=torch.uint8, device=dev)
+    d_dst = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    flags = _lib.F_VERIFY_CHECKSUM if a.verify else 0
+    status, length = decode_tensors([up(data)], [d_dst], flags=flags, prefixes=[up(old)])
+    if status[0] != 0:
+        print(f"Error: {_lib.status_name(status[0])}", file=sys.stderr)
+        return 1
+    out = bytes(d_dst[:length[0]].cpu().numpy().tobytes())
+    if a.output:
+        with open(a.output, "wb") as fo:
+            fo.write(out)
+    else:
+        sys.stdout.buffer.write(out)
+        sys.stdout.buffer.flush()
+    return 0
 
 
 def _dictionary(paths):
@@ -81,6 +120,11 @@ def main(argv=None) -> int:
     data = open(a.filename, "rb").read()
     if a.info:
         return _info(data)
+    if a.patch_from:
+        if a.dictionary:
+            print("Error: --patch-from and -D exclude one another", file=sys.stderr)
+            return 2
+        return _patch(a, data)
     import torch
     try:
         dictionary = _dictionary(a.dictionary) if a.dictionary else None

@@ -61,6 +61,12 @@ class BatchInfo(C.Structure):
                 ("host_ns", C.c_uint64), ("upload_ns", C.c_uint64)]
 
 
+class BatchInfoEx(BatchInfo):
+    """zd_batch_info as include/zd.h has it now (zd_batch_info_get_sized fills
+    it; BatchInfo is the 80 bytes zd_batch_info_get writes)."""
+    _fields_ = [("prefix_bytes_total", C.c_uint64)]
+
+
 COMM_ID_BYTES = 128
 
 # every entry point declared in include/zd.h: name -> (restype, argtypes)
@@ -102,6 +108,10 @@ SIGNATURES = {
                                   C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_create_device": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_create_device_dicts": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
+    "zd_batch_create_prefix": (C.c_int, [C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64),
+                                         C.POINTER(_vp), C.POINTER(C.c_uint64), _sz, C.c_uint32, _vp,
+                                         C.POINTER(_vp)]),
+    "zd_batch_create_device_prefix": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
     "zd_chunk_sizes_device": (C.c_int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp]),
     "zd_batch_create_device_packed": (C.c_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_create_device_packed_dicts": (C.c_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp,
@@ -109,6 +119,7 @@ SIGNATURES = {
     "zd_batch_output_layout": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(_vp)]),
     "zd_batch_bind_output": (C.c_int, [_vp, _vp, C.c_uint64]),
     "zd_batch_info_get": (C.c_int, [_vp, C.POINTER(BatchInfo)]),
+    "zd_batch_info_get_sized": (C.c_int, [_vp, C.POINTER(BatchInfoEx), _sz]),
     "zd_batch_decode_async": (C.c_int, [_vp, _vp]),
     "zd_batch_device_results": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "zd_batch_device_checksums": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

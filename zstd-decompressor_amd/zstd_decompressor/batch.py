@@ -322,10 +322,21 @@ def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, str
     return sizes, statuses, exact
 
 
+def _batch_info(h):
+    info = _lib.BatchInfoEx()
+    _lib.check(_lib.lib().zd_batch_info_get_sized(h, C.byref(info), C.sizeof(info)), "zd_batch_info_get_sized")
+    return info
+
+
 class Batch:
     """zd_batch: N independently compressed chunks at N device addresses, each
     decoded into its own device buffer with its own status (dictionary: a
-    Dictionary every chunk decodes with, or a DictionarySet).
+    Dictionary every chunk decodes with, or a DictionarySet; prefixes: a pair
+    (ptrs, sizes), chunk i decodes against the sizes[i] bytes at device address
+    ptrs[i] -- its own raw-content prefix, as ZSTD_DCtx_refPrefix gives a frame;
+    size 0, address None or 0: no prefix.  Prefixes are read by decode_async
+    where they lie, must stay valid while the batch lives and must not overlap
+    a destination; not together with dictionary=).
 
     src_ptrs / dst_ptrs are device addresses (integers, e.g. tensor.data_ptr()),
     src_sizes / dst_caps byte counts.  A chunk holds one zstd frame (skippable
@@ -333,16 +344,27 @@ class Batch:
     need no padding and may be released afterwards); the destinations must
     stay valid while the batch decodes."""
 
-    def __init__(self, src_ptrs, src_sizes, dst_ptrs, dst_caps, flags: int = 0, dictionary=None, stream: int = 0):
+    def __init__(self, src_ptrs, src_sizes, dst_ptrs, dst_caps, flags: int = 0, dictionary=None, stream: int = 0,
+                 prefixes=None):
         n = len(src_ptrs)
         if not (len(src_sizes) == len(dst_ptrs) == len(dst_caps) == n):
             raise ValueError("src_ptrs, src_sizes, dst_ptrs and dst_caps differ in length")
         if dictionary is not None and not getattr(dictionary, "_h", None):
             raise ValueError("the %s is closed" % type(dictionary).__name__)
+        if prefixes is not None and dictionary is not None:
+            raise ValueError("prefixes= and dictionary= exclude one another")
         sp, ss, dp, dc = (_u64_array(v, n) for v in (src_ptrs, src_sizes, dst_ptrs, dst_caps))
         vpp = C.POINTER(C.c_void_p)
         h = C.c_void_p()
-        if isinstance(dictionary, DictionarySet):
+        if prefixes is not None:
+            pptrs, psizes = prefixes
+            if not (len(pptrs) == len(psizes) == n):
+                raise ValueError("the prefixes and the chunks differ in length")
+            pp, ps = _u64_array(pptrs, n), _u64_array(psizes, n)
+            _lib.check(_lib.lib().zd_batch_create_prefix(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, C.cast(pp, vpp), ps,
+                                                         n, flags, C.c_void_p(stream), C.byref(h)),
+                       "zd_batch_create_prefix")
+        elif isinstance(dictionary, DictionarySet):
             _lib.check(_lib.lib().zd_batch_create_dicts(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, n, flags,
                                                         dictionary._h, C.c_void_p(stream), C.byref(h)),
                        "zd_batch_create_dicts")
@@ -353,12 +375,11 @@ class Batch:
                        "zd_batch_create")
         self._h = h
         self.nchunks = n
-        self.info = _lib.BatchInfo()
-        _lib.check(_lib.lib().zd_batch_info_get(h, C.byref(self.info)), "zd_batch_info_get")
+        self.info = _batch_info(h)
 
     @classmethod
     def from_device(cls, src_ptrs, src_sizes, dst_ptrs, dst_caps, nchunks=None, flags: int = 0, dictionary=None,
-                    stream: int = 0):
+                    stream: int = 0, prefixes=None):
         """zd_batch_create_device: the same batch from a chunk table that is on
         the device.  Each of the four arrays is a contiguous int64 / uint64
         device tensor of one entry a chunk, or the device address of such an
@@ -367,8 +388,16 @@ class Batch:
         checks and descriptors are built on the GPU.  A bad entry (a NULL
         address with a non-zero count) fails its own chunk with INVALID_ARG
         instead of the call, and overlapping destinations are not checked: the
-        caller keeps them disjoint.  `.info.device_built` is 1."""
-        arrs = (src_ptrs, src_sizes, dst_ptrs, dst_caps)
+        caller keeps them disjoint.  `.info.device_built` is 1.
+        prefixes: a pair (ptrs, sizes) of two more such arrays, chunk i's own
+        prefix (zd_batch_create_device_prefix; not together with dictionary=);
+        a NULL prefix address with a non-zero size fails its own chunk, and
+        keeping prefixes and destinations apart is the caller's duty."""
+        if prefixes is not None and dictionary is not None:
+            raise ValueError("prefixes= and dictionary= exclude one another")
+        arrs = (src_ptrs, src_sizes, dst_ptrs, dst_caps) + (tuple(prefixes) if prefixes is not None else ())
+        if len(arrs) not in (4, 6):
+            raise ValueError("prefixes is a pair (ptrs, sizes)")
         n, addr, keep = nchunks, [], []
         for a in arrs:
             if isinstance(a, int):
@@ -390,8 +419,12 @@ class Batch:
             raise ValueError("the %s is closed" % type(dictionary).__name__)
         self = cls.__new__(cls)
         h = C.c_void_p()
-        sp, ss, dp, dc = (C.c_void_p(a) for a in addr)
-        if isinstance(dictionary, DictionarySet):
+        sp, ss, dp, dc = (C.c_void_p(a) for a in addr[:4])
+        if prefixes is not None:
+            _lib.check(_lib.lib().zd_batch_create_device_prefix(sp, ss, dp, dc, C.c_void_p(addr[4]), C.c_void_p(addr[5]),
+                                                                n, flags, C.c_void_p(stream), C.byref(h)),
+                       "zd_batch_create_device_prefix")
+        elif isinstance(dictionary, DictionarySet):
             _lib.check(_lib.lib().zd_batch_create_device_dicts(sp, ss, dp, dc, n, flags, dictionary._h,
                                                                C.c_void_p(stream), C.byref(h)),
                        "zd_batch_create_device_dicts")
@@ -403,8 +436,7 @@ class Batch:
         del keep
         self._h = h
         self.nchunks = n
-        self.info = _lib.BatchInfo()
-        _lib.check(_lib.lib().zd_batch_info_get(h, C.byref(self.info)), "zd_batch_info_get")
+        self.info = _batch_info(h)
         return self
 
     @classmethod
@@ -437,8 +469,7 @@ class Batch:
         del keep
         self._h = h
         self.nchunks = n
-        self.info = _lib.BatchInfo()
-        _lib.check(_lib.lib().zd_batch_info_get(h, C.byref(self.info)), "zd_batch_info_get")
+        self.info = _batch_info(h)
         ob = C.c_uint64()
         _lib.check(_lib.lib().zd_batch_output_layout(h, C.byref(ob), None, None), "zd_batch_output_layout")
         self.out_bytes = ob.value
@@ -523,19 +554,26 @@ class Batch:
             pass
 
 
-def decode_tensors(srcs, dsts, dictionary=None, flags: int = 0):
+def decode_tensors(srcs, dsts, dictionary=None, flags: int = 0, prefixes=None):
     """Decode uint8 device tensors srcs[i] (one chunk each) into dsts[i] on
-    torch's current stream: (statuses, lengths)."""
+    torch's current stream: (statuses, lengths).  prefixes: one entry a chunk,
+    a uint8 device tensor (the chunk's own prefix, read in place) or None."""
     import torch
     if len(srcs) != len(dsts):
         raise ValueError("srcs and dsts differ in length")
-    for t in list(srcs) + list(dsts):
+    if prefixes is not None and len(prefixes) != len(srcs):
+        raise ValueError("srcs and prefixes differ in length")
+    for t in list(srcs) + list(dsts) + [p for p in (prefixes or ()) if p is not None]:
         if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
             raise ValueError("contiguous uint8 device tensors required")
     stream = torch.cuda.current_stream().cuda_stream
+    pfx = None
+    if prefixes is not None:
+        pfx = ([p.data_ptr() if p is not None and p.numel() else 0 for p in prefixes],
+               [p.numel() if p is not None else 0 for p in prefixes])
     b = Batch([t.data_ptr() if t.numel() else 0 for t in srcs], [t.numel() for t in srcs],
               [t.data_ptr() if t.numel() else 0 for t in dsts], [t.numel() for t in dsts],
-              flags=flags, dictionary=dictionary, stream=stream)
+              flags=flags, dictionary=dictionary, stream=stream, prefixes=pfx)
     try:
         b.decode_async(stream)
         return b.results(stream)
