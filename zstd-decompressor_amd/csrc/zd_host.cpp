@@ -50,6 +50,12 @@ struct VecSink {
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { \
   fprintf(stderr, "zd: %s failed: %s\n", #x, hipGetErrorString(_e)); return ZD_E_HIP; } } while (0)
 
+using TimePoint = std::chrono::steady_clock::time_point;
+uint64_t ns(TimePoint a, TimePoint b) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count(); }
+
+// hipFree as a deleter
+struct Free { void operator()(void* p) const { if (p) (void)hipFree(p); } };
+
 }  // namespace
 
 // ===========================================================================
@@ -698,6 +704,19 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
   return 0;
 }
 
+// build_plan for a plan or a batch, staged.  With one dictionary (P->dict) its
+// tables are the prebuilt comp 0 (a raw-content dictionary has none), its
+// repeat offsets every frame's first, and its content the positions before
+// every frame; a dictionary set gives every frame's from the plan's table
+// (PlanCtx::dset).
+int build_plan_staged(zd_plan* P) {
+  const int32_t none[3] = {-1, -1, -1}, pre[3] = {0, 0, 0};
+  const uint64_t rep0[3] = {1, 4, 8};
+  const DictData* D = P->dict.get();
+  return D ? build_plan(P, D->raw ? -1 : 0, D->raw ? none : pre, D->content, D->rep, 0, true)
+           : build_plan(P, -1, none, 0, rep0, 0, true);
+}
+
 // Device workspaces of destroyed plans, kept for the next plans of this
 // process (a plan's workspace is up to ~1.2x its decoded bytes: K3's
 // records, the literals, the tables).  A plan takes a cached block of at
@@ -1080,6 +1099,15 @@ DevWalkBufs& dev_walk_bufs() {
   static DevWalkBufs* b = new DevWalkBufs();
   return *b;
 }
+// The walk's device buffers are `dev`'s from here on: those of another device
+// start over.  The caller holds B.m.
+void walk_bufs_on(DevWalkBufs& B, int dev) {
+  if (B.dev == dev) return;
+  if (B.d_wr) (void)hipFree(B.d_wr);
+  if (B.d_out) (void)hipFree(B.d_out);
+  B.d_wr = nullptr; B.cap_wr = 0; B.d_out = nullptr; B.cap_out = 0;
+  B.dev = dev;
+}
 
 template <typename T>
 bool grow_dev(T*& p, size_t& cap, size_t need) {
@@ -1350,9 +1378,7 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
     if (!P->d_prefix_ptrs) return ZD_E_INVALID_ARG;
     HIPCHK(hipMemcpyAsync(b + W.dict_ptrs, P->d_prefix_ptrs, 8 * F, hipMemcpyDeviceToDevice, s));
   }
-  if (in)
-    in->alloc_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - ta)
-                       .count();
+  if (in) in->alloc_ns = ns(ta, std::chrono::steady_clock::now());
   uint64_t* d_fout = B.d_fo;
   uint64_t* d_fcap = B.d_fo + std::max<uint64_t>(F, 1);
   const Sink S{(CompBlock*)(b + W.comp), (BlockRec*)(b + W.blocks), (FrameDesc*)(b + W.frames),
@@ -1396,12 +1422,7 @@ int plan_index_dev(zd_plan* P, const uint8_t* d_src, size_t n, hipStream_t s) {
     std::lock_guard<std::mutex> lk(B.m);
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (B.dev != dev) {                      // buffers of another device: start over
-      if (B.d_wr) (void)hipFree(B.d_wr);
-      if (B.d_out) (void)hipFree(B.d_out);
-      B.d_wr = nullptr; B.cap_wr = 0; B.d_out = nullptr; B.cap_out = 0;
-      B.dev = dev;
-    }
+    walk_bufs_on(B, dev);
     const uint64_t chunk = std::max<uint64_t>(256u << 10, (n + 16383) / 16384);
     const uint32_t T = (uint32_t)((n + chunk - 1) / chunk);
     uint64_t F = 0, NB = 0;
@@ -1715,20 +1736,8 @@ static int plan_create(const uint8_t* src, const uint8_t* d_src, size_t n, uint3
     plan_index(P, src, n);
   }
   const auto ti = std::chrono::steady_clock::now();
-  int32_t none[3] = {-1, -1, -1};
-  uint64_t rep0[3] = {1, 4, 8};
-  if (dict) {
-    // the dictionary's tables are the prebuilt comp 0 (a raw-content
-    // dictionary has none), its repeat offsets every frame's first, and its
-    // content the positions before every frame
-    const int32_t pre[3] = {0, 0, 0};
-    if (int r = build_plan(P, dict->raw ? -1 : 0, dict->raw ? none : pre, dict->content, dict->rep, 0, true)) {
-      zd_plan_destroy(P);
-      return r;
-    }
-  } else if (!P->dev_built)
-    // (a dictionary set: every frame's dictionary from the plan's table, PlanCtx::dset)
-    if (int r = build_plan(P, -1, none, 0, rep0, 0, true)) { zd_plan_destroy(P); return r; }
+  if (dict || !P->dev_built)
+    if (int r = build_plan_staged(P)) { zd_plan_destroy(P); return r; }
   P->info.src_bytes = n;
   const auto t1 = std::chrono::steady_clock::now();
   dump_plan_desc(P);
@@ -1748,8 +1757,8 @@ static int plan_create(const uint8_t* src, const uint8_t* d_src, size_t n, uint3
     fprintf(stderr, "zd plan: workspace + upload %.2f ms, streams %.2f ms\n",
             std::chrono::duration<double, std::milli>(tu - t1).count(),
             std::chrono::duration<double, std::milli>(t2 - tu).count());
-  P->info.host_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
-  P->info.device_ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t2 - t1).count();
+  P->info.host_ns = ns(t0, t1);
+  P->info.device_ns = ns(t1, t2);
   *out = P;
   return ZD_OK;
 }
@@ -2214,7 +2223,6 @@ int zd_plan_decompress(zd_plan* P, const uint8_t* src, size_t n, uint8_t* dst, s
   if (copy && dst)
     if (int e = io_d2h(dst, o.p, copy, s, io_ring(), ev.e)) return e;
   const auto t3 = std::chrono::steady_clock::now();
-  auto ns = [](auto a, auto b) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count(); };
   P->info.io_h2d_ns = ns(t0, t1);
   P->info.io_decode_ns = ns(t1, t2);
   P->info.io_d2h_ns = ns(t2, t3);
@@ -2433,13 +2441,13 @@ struct zd_batch {
   bool device_built = false;
   uint64_t *d_cap = nullptr, *d_piece0 = nullptr;
   uint8_t* d_flag = nullptr;
+  uint64_t *d_scratch = nullptr, *d_res = nullptr;   // creation's scans and the words that come back
   // a packed batch (zd_batch_create_device_packed): d_out / d_cap are its own
   // layout, outbase the bound buffer (zd_batch_bind_output; null until then)
   bool packed = false;
   uint64_t out_bytes = 0;
-  // a prefix batch (zd_batch_create_prefix / _device_prefix); made from device
-  // arrays: the checked prefix addresses and sizes, in d_arr
-  bool prefix = false;
+  // a prefix batch made from device arrays (zd_batch_create_device_prefix):
+  // the checked prefix addresses and sizes, in d_arr
   uint64_t *d_pfx = nullptr, *d_pfx_bytes = nullptr;
   int host_arrays() {
     if (!device_built || goff.size() == n) return 0;
@@ -2473,374 +2481,256 @@ void zd_batch_destroy(zd_batch* B) {
   delete B;
 }
 
-// zd_batch_create / zd_batch_create_dicts / zd_batch_create_prefix: one
-// dictionary, a set, a prefix per chunk (`with_prefix`; d_prefix / prefix_bytes
-// host arrays), or none of them
-static int batch_create(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
-                        const uint64_t* dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
-                        const zd_dict_set* set, void* stream, zd_batch** out, bool with_prefix = false,
-                        const void* const* d_prefix = nullptr, const uint64_t* prefix_bytes = nullptr) {
-  // ---- argument checks: no HIP call before they are done ----
-  if (!out || (flags & ZD_F_SKIPPABLE)) return ZD_E_INVALID_ARG;
-  if (nchunks && (!d_src || !src_bytes || !d_dst || !dst_cap)) return ZD_E_INVALID_ARG;
-  if (with_prefix && (dict || set || (nchunks && (!d_prefix || !prefix_bytes)))) return ZD_E_INVALID_ARG;
-  if (nchunks >= (1ull << 31) || (dict && !dict->p) || (set && !set->p)) return ZD_E_INVALID_ARG;
-  const size_t n = nchunks;
-  {
-    std::vector<std::pair<uint64_t, uint64_t>> ranges;      // destinations of at least one byte
-    for (size_t i = 0; i < n; i++) {
-      if ((!d_src[i] && src_bytes[i]) || (!d_dst[i] && dst_cap[i])) return ZD_E_INVALID_ARG;
-      const uint64_t a = (uint64_t)(uintptr_t)d_dst[i];
-      if (a + dst_cap[i] < a || (uint64_t)(uintptr_t)d_src[i] + src_bytes[i] < (uint64_t)(uintptr_t)d_src[i])
-        return ZD_E_INVALID_ARG;
-      if (dst_cap[i]) ranges.push_back({a, dst_cap[i]});
-    }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t k = 1; k < ranges.size(); k++)
-      if (ranges[k].first < ranges[k - 1].first + ranges[k - 1].second) return ZD_E_INVALID_ARG;
-    // a prefix is read while the destinations are written: no prefix range may
-    // meet one (the sorted destinations are disjoint, so of those that start
-    // below the prefix's end the last one reaches furthest)
-    for (size_t i = 0; with_prefix && i < n; i++) {
-      const uint64_t a = (uint64_t)(uintptr_t)d_prefix[i], z = prefix_bytes[i];
-      if ((!a && z) || a + z < a) return ZD_E_INVALID_ARG;
-      if (!z) continue;
-      auto it = std::lower_bound(ranges.begin(), ranges.end(), std::pair<uint64_t, uint64_t>{a + z, 0});
-      if (it != ranges.begin() && (it - 1)->first + (it - 1)->second > a) return ZD_E_INVALID_ARG;
-    }
-  }
-  zd_batch* B = new (std::nothrow) zd_batch();
-  if (!B) return ZD_E_NO_MEMORY;
-  struct Drop { void operator()(zd_batch* b) const { zd_batch_destroy(b); } };
-  std::unique_ptr<zd_batch, Drop> hold(B);
-  B->n = n;
-  B->flags = flags;
-  B->info.nchunks = n;
-  B->prefix = with_prefix;
-  if (!n) { *out = hold.release(); return ZD_OK; }
+// What a batch is made from: every zd_batch_create* entry point fills one.
+struct BatchSpec {
+  // one entry a chunk: host arrays, or with on_device device arrays readable on `stream`
+  const void* const* src = nullptr;
+  const uint64_t* src_bytes = nullptr;
+  void* const* dst = nullptr;              // (both null: a packed batch)
+  const uint64_t* dst_cap = nullptr;
+  const void* const* prefix = nullptr;     // (both null: no prefixes)
+  const uint64_t* prefix_bytes = nullptr;
+  bool on_device = false;
+  size_t n = 0;
+  uint32_t flags = 0;
+  uint32_t align = 0;                      // a packed batch's alignment (device arrays only); 0: not packed
+  std::shared_ptr<DictData> dict;          // one dictionary, a set, prefixes, or none of them
+  std::shared_ptr<DictSetData> dset;
+  hipStream_t stream = nullptr;
+  bool packed() const { return align != 0; }
+  bool with_prefix() const { return prefix || prefix_bytes; }
+};
+// (an entry point's handles: false for one without data)
+static bool spec_dicts(BatchSpec& S, const zd_dict* dict, const zd_dict_set* set) {
+  if ((dict && !dict->p) || (set && !set->p)) return false;
+  if (dict) S.dict = dict->p;
+  if (set) S.dset = set->p;
+  return true;
+}
 
-  HIPCHK(hipGetDevice(&B->dev));
-  if (dict) {
-    if (dict->p->dev != B->dev) return ZD_E_INVALID_ARG;
-    B->dict = dict->p;
+struct Drop { void operator()(zd_batch* b) const { zd_batch_destroy(b); } };
+
+// d_arr and every array in it, as carved
+static int batch_arrays(zd_batch* B, const BatchCarve& C) {
+  B->arr_bytes = C.total;
+  HIPCHK(hipMalloc(&B->d_arr, B->arr_bytes));
+  const auto at = [&](uint64_t o) { return o == BatchCarve::ABSENT ? nullptr : B->d_arr + o; };
+  B->d_src = (uint64_t*)at(C.src); B->d_size = (uint64_t*)at(C.size); B->d_off = (uint64_t*)at(C.off);
+  B->d_out = (uint64_t*)at(C.out);
+  B->d_pieces = (GatherPiece*)at(C.pieces);
+  static_assert(sizeof(GatherPiece) == 8, "GatherPiece: one u64 slot");
+  B->d_boff = (uint64_t*)at(C.boff); B->d_len = (uint64_t*)at(C.len); B->d_hash = (uint64_t*)at(C.hash);
+  B->d_status = (int32_t*)at(C.status);
+  B->d_nblk = (uint32_t*)at(C.nblk);
+  B->d_bind = at(C.bind);
+  B->d_piece0 = (uint64_t*)at(C.piece0); B->d_cap = (uint64_t*)at(C.cap);
+  B->d_flag = at(C.flag);
+  B->d_scratch = (uint64_t*)at(C.scratch); B->d_res = (uint64_t*)at(C.res);
+  B->d_pfx = (uint64_t*)at(C.pfx); B->d_pfx_bytes = (uint64_t*)at(C.pfx_bytes);
+  return 0;
+}
+
+// Host arrays: every entry is checked here, and a bad one fails the call
+static int check_entries(const BatchSpec& S) {
+  std::vector<std::pair<uint64_t, uint64_t>> ranges;      // destinations of at least one byte
+  for (size_t i = 0; i < S.n; i++) {
+    if ((!S.src[i] && S.src_bytes[i]) || (!S.dst[i] && S.dst_cap[i])) return ZD_E_INVALID_ARG;
+    const uint64_t a = (uint64_t)(uintptr_t)S.dst[i];
+    if (a + S.dst_cap[i] < a || (uint64_t)(uintptr_t)S.src[i] + S.src_bytes[i] < (uint64_t)(uintptr_t)S.src[i])
+      return ZD_E_INVALID_ARG;
+    if (S.dst_cap[i]) ranges.push_back({a, S.dst_cap[i]});
   }
-  if (set) {
-    if (set->p->dev != B->dev) return ZD_E_INVALID_ARG;
-    B->dset = set->p;
+  std::sort(ranges.begin(), ranges.end());
+  for (size_t k = 1; k < ranges.size(); k++)
+    if (ranges[k].first < ranges[k - 1].first + ranges[k - 1].second) return ZD_E_INVALID_ARG;
+  // a prefix is read while the destinations are written: no prefix range may
+  // meet one (the sorted destinations are disjoint, so of those that start
+  // below the prefix's end the last one reaches furthest)
+  for (size_t i = 0; S.with_prefix() && i < S.n; i++) {
+    const uint64_t a = (uint64_t)(uintptr_t)S.prefix[i], z = S.prefix_bytes[i];
+    if ((!a && z) || a + z < a) return ZD_E_INVALID_ARG;
+    if (!z) continue;
+    auto it = std::lower_bound(ranges.begin(), ranges.end(), std::pair<uint64_t, uint64_t>{a + z, 0});
+    if (it != ranges.begin() && (it - 1)->first + (it - 1)->second > a) return ZD_E_INVALID_ARG;
   }
-  const hipStream_t s = (hipStream_t)stream;
-  const auto t0 = std::chrono::steady_clock::now();
-  // ---- the gathered layout and zd_k_gather's pieces ----
+  return 0;
+}
+
+// What the phases of a creation from host arrays hand on
+struct HostArrays {
+  std::vector<uint64_t> head;        // d_arr's uploaded head (kept to the end of the call)
+  const uint64_t* out = nullptr;     //   its out column: the plan's place_out
+  std::vector<uint8_t> bind;         // the capacity pass's flags, uploaded after the descriptors
+};
+
+// Host arrays: the gathered layout and zd_k_gather's pieces, made here and
+// uploaded as d_arr's head; then the gather.  info.gathered_bytes is set.
+static int gather_host(const BatchSpec& S, zd_batch* B, HostArrays& H) {
+  const size_t n = S.n;
+  const hipStream_t s = S.stream;
   B->goff.resize(n);
-  B->src_size.assign(src_bytes, src_bytes + n);
+  B->src_size.assign(S.src_bytes, S.src_bytes + n);
   B->dst.resize(n);
-  B->dst_cap.assign(dst_cap, dst_cap + n);
+  B->dst_cap.assign(S.dst_cap, S.dst_cap + n);
   uint64_t total = 0, npieces = 0;
   uint64_t lowest = UINT64_MAX;
   for (size_t i = 0; i < n; i++) {
     B->goff[i] = total;
-    total += align_up(src_bytes[i], 16) + ZD_SRC_PADDING;
-    npieces += std::max<uint64_t>(1, (src_bytes[i] + COPY_PIECE - 1) / COPY_PIECE);
-    B->dst[i] = (uint64_t)(uintptr_t)d_dst[i];
-    if (d_dst[i]) lowest = std::min(lowest, B->dst[i]);
+    total += align_up(S.src_bytes[i], 16) + ZD_SRC_PADDING;
+    npieces += std::max<uint64_t>(1, (S.src_bytes[i] + COPY_PIECE - 1) / COPY_PIECE);
+    B->dst[i] = (uint64_t)(uintptr_t)S.dst[i];
+    if (S.dst[i]) lowest = std::min(lowest, B->dst[i]);
   }
   if (lowest == UINT64_MAX) lowest = 0;
   if (npieces * (COPY_PIECE / 4096) >= (1ull << 31)) return ZD_E_OUT_OF_DOMAIN;   // zd_k_gather's grid
   B->outbase = (uint8_t*)(uintptr_t)lowest;
-  // the uploaded head of d_arr: src | size | off | out | pieces; then the device-written arrays
-  const uint64_t head_words = 4 * n + npieces;
-  std::vector<uint64_t> head(head_words);
+  BatchCarve C;
+  C.carve(n, false, npieces, false);
+  std::vector<uint64_t>& head = H.head;
+  head.resize(C.head_bytes / 8);
+  uint64_t *h_src = head.data() + C.src / 8, *h_size = head.data() + C.size / 8, *h_off = head.data() + C.off / 8,
+           *h_out = head.data() + C.out / 8;
   for (size_t i = 0; i < n; i++) {
-    head[i] = (uint64_t)(uintptr_t)d_src[i];
-    head[n + i] = src_bytes[i];
-    head[2 * n + i] = B->goff[i];
-    head[3 * n + i] = d_dst[i] ? B->dst[i] - lowest : 0;
+    h_src[i] = (uint64_t)(uintptr_t)S.src[i];
+    h_size[i] = S.src_bytes[i];
+    h_off[i] = B->goff[i];
+    h_out[i] = S.dst[i] ? B->dst[i] - lowest : 0;
   }
+  H.out = h_out;
   {
-    GatherPiece* gp = (GatherPiece*)(head.data() + 4 * n);
-    static_assert(sizeof(GatherPiece) == 8, "GatherPiece: one u64 slot");
+    GatherPiece* gp = (GatherPiece*)(head.data() + C.pieces / 8);
     uint64_t k = 0;
     for (size_t i = 0; i < n; i++) {
-      const uint64_t np = std::max<uint64_t>(1, (src_bytes[i] + COPY_PIECE - 1) / COPY_PIECE);
+      const uint64_t np = std::max<uint64_t>(1, (S.src_bytes[i] + COPY_PIECE - 1) / COPY_PIECE);
       if (np >= (1ull << 32)) return ZD_E_OUT_OF_DOMAIN;
       for (uint64_t q = 0; q < np; q++) gp[k++] = GatherPiece{(uint32_t)i, (uint32_t)q};
     }
   }
-  B->arr_bytes = 8 * (head_words + 3 * n) + 4 * n + 4 * n + align_up(n, 8);
-  HIPCHK(hipMalloc(&B->d_arr, B->arr_bytes));
-  {
-    uint64_t* a = (uint64_t*)B->d_arr;
-    B->d_src = a; B->d_size = a + n; B->d_off = a + 2 * n; B->d_out = a + 3 * n;
-    B->d_pieces = (GatherPiece*)(a + 4 * n);
-    B->d_boff = a + head_words; B->d_len = B->d_boff + n; B->d_hash = B->d_len + n;
-    B->d_status = (int32_t*)(B->d_hash + n);
-    B->d_nblk = (uint32_t*)(B->d_status + n);
-    B->d_bind = (uint8_t*)(B->d_nblk + n);
-  }
+  if (int r = batch_arrays(B, C)) return r;
   HIPCHK(ws_alloc(B->dev, std::max<uint64_t>(total, 16), &B->d_gather, &B->gather_alloc));
-  HIPCHK(hipMemcpyAsync(B->d_arr, head.data(), 8 * head_words, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(B->d_boff, 0, B->arr_bytes - 8 * head_words, s));
-  const ChunkList L{B->d_src, B->d_size, B->d_off};
-  HIPCHK(launch_gather(L, B->d_gather, B->d_pieces, npieces, s));
+  HIPCHK(hipMemcpyAsync(B->d_arr, head.data(), C.head_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(B->d_arr + C.head_bytes, 0, C.total - C.head_bytes, s));
+  HIPCHK(launch_gather(ChunkList{B->d_src, B->d_size, B->d_off}, B->d_gather, B->d_pieces, npieces, s));
   HIPCHK(hipStreamSynchronize(s));
-  const auto t1 = std::chrono::steady_clock::now();
-
-  // ---- zd_k_walk_chunks: count, the blocks' places, fill; the index comes back ----
-  zd_plan* P = new (std::nothrow) zd_plan();
-  if (!P) return ZD_E_NO_MEMORY;
-  B->P = P;
-  P->flags = flags;
-  P->dict = B->dict;
-  P->dset = B->dset;
-  if (with_prefix) {
-    P->prefix = true;
-    P->prefix_ptrs.resize(n);
-    P->prefix_bytes.assign(prefix_bytes, prefix_bytes + n);
-    for (size_t i = 0; i < n; i++) {
-      P->prefix_ptrs[i] = prefix_bytes[i] ? (uint64_t)(uintptr_t)d_prefix[i] : 0;
-      B->info.prefix_bytes_total += prefix_bytes[i];
-    }
-  }
-  const bool rfc_empty_lits = P->with_dict();
-  std::vector<uint8_t> bind(n, 0);
-  P->place_out.assign(head.begin() + 3 * (long)n, head.begin() + 4 * (long)n);
-  P->place_cap = B->dst_cap;
-  {
-    DevWalkBufs& WB = dev_walk_bufs();
-    std::lock_guard<std::mutex> lk(WB.m);
-    if (WB.dev != B->dev) {                  // buffers of another device: start over
-      if (WB.d_wr) (void)hipFree(WB.d_wr);
-      if (WB.d_out) (void)hipFree(WB.d_out);
-      WB.d_wr = nullptr; WB.cap_wr = 0; WB.d_out = nullptr; WB.cap_out = 0;
-      WB.dev = B->dev;
-    }
-    HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, nullptr, nullptr, nullptr, false,
-                              s));
-    std::vector<uint32_t> nblk(n);
-    HIPCHK(hipMemcpyAsync(nblk.data(), B->d_nblk, 4 * n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<uint64_t> boff(n);
-    uint64_t NB = 0;
-    for (size_t i = 0; i < n; i++) { boff[i] = NB; NB += nblk[i]; }
-    if (NB >= (1ull << 32)) return ZD_E_OUT_OF_DOMAIN;
-    const size_t fb = align_up(n * sizeof(HostFrame), 256), bytes = fb + NB * sizeof(HostBlock);
-    if (!grow_dev(WB.d_out, WB.cap_out, bytes) || !grow_pinned(WB.h_out, WB.cap_h, bytes)) return ZD_E_HIP;
-    WB.fb = fb;
-    WB.bytes = bytes;
-    HIPCHK(hipMemcpyAsync(B->d_boff, boff.data(), 8 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, B->d_boff, (HostFrame*)WB.d_out,
-                              (HostBlock*)(WB.d_out + fb), true, s));
-    const HostFrame* cfr = nullptr;
-    const HostBlock* bl = nullptr;
-    if (int r = dev_walk_download(WB, s, &cfr, &bl)) return r;
-    // a usable Frame_Content_Size above the chunk's capacity: found here, and
-    // nothing of the chunk runs; bind: the caller's capacity is below what the
-    // plan reserves for a frame without a usable one
-    HostFrame* fr = (HostFrame*)WB.h_out;
-    std::vector<const HostFrame*> kept(n);
-    for (size_t i = 0; i < n; i++) {
-      HostFrame& hf = fr[i];
-      kept[i] = &hf;
-      if (hf.d.kind != ZD_FRAME_ZSTD || hf.key != KEY_NONE) continue;
-      uint64_t bound = 0;
-      for (uint32_t k = 0; k < hf.nb; k++) bound += bl[hf.b0 + k].type == 2 ? MAX_BLOCK_OUT : bl[hf.b0 + k].size;
-      const bool usable = hf.d.content_size != UINT64_MAX && hf.d.content_size <= bound;
-      if (usable && hf.d.content_size > dst_cap[i]) {
-        hf.status = ZD_E_DST_TOO_SMALL;
-        hf.key = make_key(PH_LIMIT, 0, 0, 0, ZD_E_DST_TOO_SMALL);
-      }
-      bind[i] = !usable && dst_cap[i] < bound;
-    }
-    std::vector<HostPart> parts;
-    parts_from(kept, bl, parts);
-    P->set_parts(std::move(parts));
-  }
-  P->index_status = 0;
-  P->index_stop = P->nframes;
-  const auto t2 = std::chrono::steady_clock::now();
-
-  // ---- descriptors (host), placed at the chunks' destinations ----
-  {
-    const int32_t none[3] = {-1, -1, -1}, pre[3] = {0, 0, 0};
-    const uint64_t rep0[3] = {1, 4, 8};
-    const DictData* D = B->dict.get();
-    const int r = D ? build_plan(P, D->raw ? -1 : 0, D->raw ? none : pre, D->content, D->rep, 0, true)
-                    : build_plan(P, -1, none, 0, rep0, 0, true);
-    if (r) return r;
-  }
-  P->info.src_bytes = total;
-  const auto t3 = std::chrono::steady_clock::now();
-  if (int r = upload_desc(P)) return r;
-  if (int r = upload_dict_tables(P)) return r;
-  HIPCHK(hipMemcpy(B->d_bind, bind.data(), n, hipMemcpyHostToDevice));
-  if (!aux_take(P)) return ZD_E_HIP;
-  const auto t4 = std::chrono::steady_clock::now();
-  auto ns = [](auto a, auto b) {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count();
-  };
-  zd_batch_info& I = B->info;
-  I.gathered_bytes = total;
-  I.nblocks = P->info.nblocks;
-  I.nsequences = P->info.nsequences;
-  I.workspace_bytes = P->W.total + B->arr_bytes;
-  I.executors = P->info.executors;
-  I.gather_ns = ns(t0, t1);
-  I.walk_ns = ns(t1, t2);
-  I.host_ns = ns(t2, t3);
-  I.upload_ns = ns(t3, t4);
-  *out = hold.release();
-  return ZD_OK;
+  B->info.gathered_bytes = total;
+  return 0;
 }
 
-int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst, const uint64_t* dst_cap,
-                    size_t nchunks, uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out) {
-  return batch_create(d_src, src_bytes, d_dst, dst_cap, nchunks, flags, dict, nullptr, stream, out);
-}
-
-int zd_batch_create_prefix(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
-                           const uint64_t* dst_cap, const void* const* d_prefix, const uint64_t* prefix_bytes,
-                           size_t nchunks, uint32_t flags, void* stream, zd_batch** out) {
-  return batch_create(d_src, src_bytes, d_dst, dst_cap, nchunks, flags, nullptr, nullptr, stream, out, true, d_prefix,
-                      prefix_bytes);
-}
-
-int zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
-                          const uint64_t* dst_cap, size_t nchunks, uint32_t flags, const zd_dict_set* set, void* stream,
-                          zd_batch** out) {
-  if (!set) return ZD_E_INVALID_ARG;
-  return batch_create(d_src, src_bytes, d_dst, dst_cap, nchunks, flags, nullptr, set, stream, out);
-}
-
-// zd_batch_create_device / zd_batch_create_device_dicts: batch_create with the
-// four arrays on the device.  Layout, gather, walk, capacity pass and
-// descriptors all run there; the host reads back a few words a phase (the
-// layout's totals, the block count, the routing shape and a set's used flags,
-// the plan's totals) and the frames' output offsets and capacities.
-// align != 0: a packed batch (zd_batch_create_device_packed): no destination
-// arrays; after the fill pass zd_k_batch_pack and one scan write the chunks'
-// capacities (their reserves) and offsets into d_cap / d_out, and the capacity
-// pass and the planner run on those.
-static int batch_create_device(const void* const* d_src, const uint64_t* d_src_bytes, void* const* d_dst,
-                               const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
-                               const zd_dict_set* set, void* stream, zd_batch** out, uint32_t align = 0,
-                               bool with_prefix = false, const void* const* d_prefix = nullptr,
-                               const uint64_t* d_prefix_bytes = nullptr) {
-  // ---- argument checks: no HIP call before they are done ----
-  const bool packed = align != 0;
-  if (!out || (flags & ZD_F_SKIPPABLE)) return ZD_E_INVALID_ARG;
-  if (with_prefix && (dict || set || packed || (nchunks && (!d_prefix || !d_prefix_bytes)))) return ZD_E_INVALID_ARG;
-  if (nchunks && (!d_src || !d_src_bytes || (!packed && (!d_dst || !d_dst_cap)))) return ZD_E_INVALID_ARG;
-  if (nchunks >= (1ull << 31) || (dict && !dict->p) || (set && !set->p)) return ZD_E_INVALID_ARG;
-  const size_t n = nchunks;
-  zd_batch* B = new (std::nothrow) zd_batch();
-  if (!B) return ZD_E_NO_MEMORY;
-  struct Drop { void operator()(zd_batch* b) const { zd_batch_destroy(b); } };
-  std::unique_ptr<zd_batch, Drop> hold(B);
-  B->n = n;
-  B->flags = flags;
-  B->device_built = true;
-  B->packed = packed;
-  B->prefix = with_prefix;
-  B->info.nchunks = n;
-  B->info.device_built = 1;
-  if (!n) { *out = hold.release(); return ZD_OK; }
-
-  HIPCHK(hipGetDevice(&B->dev));
-  if (dict) {
-    if (dict->p->dev != B->dev) return ZD_E_INVALID_ARG;
-    B->dict = dict->p;
-  }
-  if (set) {
-    if (set->p->dev != B->dev) return ZD_E_INVALID_ARG;
-    B->dset = set->p;
-  }
-  const hipStream_t s = (hipStream_t)stream;
-  auto ns = [](auto a, auto b) {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count();
-  };
-  const auto t0 = std::chrono::steady_clock::now();
-  // d_arr: src | size | off | piece0 | out | cap | boff | len | hash (u64), status | nblk (u32), bind | flag
-  // (u8), then the scans' scratch and the words that come back
-  const uint64_t nt = (n + 255) / 256;
-  const uint64_t scratch_words = 2 * (nt + 1) + 1, res_words = 4;
-  const uint64_t bytes_at = 9 * 8 * n + 2 * 4 * n, words_at = align_up(bytes_at + 2 * n, 8);
-  // (a prefix batch: the prefixes' addresses and sizes after everything else)
-  const uint64_t pfx_at = words_at + 8 * (scratch_words + res_words);
-  B->arr_bytes = pfx_at + (with_prefix ? 2 * 8 * n : 0);
-  HIPCHK(hipMalloc(&B->d_arr, B->arr_bytes));
-  if (with_prefix) { B->d_pfx = (uint64_t*)(B->d_arr + pfx_at); B->d_pfx_bytes = B->d_pfx + n; }
-  uint64_t* a = (uint64_t*)B->d_arr;
-  B->d_src = a; B->d_size = a + n; B->d_off = a + 2 * n; B->d_piece0 = a + 3 * n; B->d_out = a + 4 * n;
-  B->d_cap = a + 5 * n; B->d_boff = a + 6 * n; B->d_len = a + 7 * n; B->d_hash = a + 8 * n;
-  B->d_status = (int32_t*)(a + 9 * n);
-  B->d_nblk = (uint32_t*)(B->d_status + n);
-  B->d_bind = B->d_arr + bytes_at;
-  B->d_flag = B->d_bind + n;
-  uint64_t* d_scratch = (uint64_t*)(B->d_arr + words_at);
-  uint64_t* d_res = d_scratch + scratch_words;
+// Device arrays: zd_k_batch_layout checks the entries (a bad one fails its
+// own chunk), lays the gathered buffer out and finds the lowest destination;
+// the totals come back, then the gather over the scanned piece starts.  `lk`
+// (WB.m) is taken here and held to the end of the call: the rest of the
+// creation reads through WB's pinned words and device buffers.
+static int gather_device(const BatchSpec& S, zd_batch* B, DevWalkBufs& WB, std::unique_lock<std::mutex>& lk) {
+  const size_t n = S.n;
+  const hipStream_t s = S.stream;
+  BatchCarve C;
+  C.carve(n, true, 0, S.with_prefix());
+  if (int r = batch_arrays(B, C)) return r;
   HIPCHK(hipMemsetAsync(B->d_arr, 0, B->arr_bytes, s));
-
-  DevWalkBufs& WB = dev_walk_bufs();
-  std::lock_guard<std::mutex> lk(WB.m);        // (its pinned words and device buffers, to the end of the call)
-  if (WB.dev != B->dev) {                      // buffers of another device: start over
-    if (WB.d_wr) (void)hipFree(WB.d_wr);
-    if (WB.d_out) (void)hipFree(WB.d_out);
-    WB.d_wr = nullptr; WB.cap_wr = 0; WB.d_out = nullptr; WB.cap_out = 0;
-    WB.dev = B->dev;
-  }
+  lk.lock();
+  walk_bufs_on(WB, B->dev);
   if (!WB.h_small && hipHostMalloc((void**)&WB.h_small, 64 * 8, hipHostMallocDefault) != hipSuccess) return ZD_E_HIP;
-
-  // ---- layout: the entries' checks, the gathered offsets, the pieces, the lowest destination ----
   const BatchArrays A{B->d_src, B->d_size, B->d_off, B->d_piece0, B->d_out, B->d_cap, B->d_flag, B->d_pfx, B->d_pfx_bytes};
-  HIPCHK(launch_batch_layout((const uint64_t*)d_src, d_src_bytes, (const uint64_t*)d_dst, d_dst_cap, (uint32_t)n, A,
-                             d_scratch, d_res, s, with_prefix ? (const uint64_t*)d_prefix : nullptr, d_prefix_bytes));
-  HIPCHK(hipMemcpyAsync(WB.h_small, d_res, 4 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(launch_batch_layout((const uint64_t*)S.src, S.src_bytes, (const uint64_t*)S.dst, S.dst_cap, (uint32_t)n, A,
+                             B->d_scratch, B->d_res, s, (const uint64_t*)S.prefix, S.prefix_bytes));
+  HIPCHK(hipMemcpyAsync(WB.h_small, B->d_res, 4 * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   const uint64_t total = WB.h_small[0], npieces = WB.h_small[1];
-  if (with_prefix) B->info.prefix_bytes_total = WB.h_small[3];
+  if (S.with_prefix()) B->info.prefix_bytes_total = WB.h_small[3];
   B->outbase = (uint8_t*)(uintptr_t)WB.h_small[2];
   if (npieces * (COPY_PIECE / 4096) >= (1ull << 31)) return ZD_E_OUT_OF_DOMAIN;   // zd_k_gather's grid
   HIPCHK(ws_alloc(B->dev, std::max<uint64_t>(total, 16), &B->d_gather, &B->gather_alloc));
-  const ChunkList L{B->d_src, B->d_size, B->d_off};
-  HIPCHK(launch_gather_scan(L, B->d_gather, B->d_piece0, (uint32_t)n, npieces, s));
+  HIPCHK(launch_gather_scan(ChunkList{B->d_src, B->d_size, B->d_off}, B->d_gather, B->d_piece0, (uint32_t)n, npieces, s));
   HIPCHK(hipStreamSynchronize(s));             // (the sources may be released from here on; gather_ns ends here)
-  const auto t1 = std::chrono::steady_clock::now();
+  B->info.gathered_bytes = total;
+  return 0;
+}
 
-  // ---- zd_k_walk_chunks: count, the blocks' places (a scan), fill; then the capacity pass ----
-  zd_plan* P = new (std::nothrow) zd_plan();
-  if (!P) return ZD_E_NO_MEMORY;
-  B->P = P;
-  P->flags = flags;
-  P->dict = B->dict;
-  P->dset = B->dset;
-  if (with_prefix) { P->prefix = true; P->d_prefix_ptrs = B->d_pfx; P->d_prefix_bytes = B->d_pfx_bytes; }
-  const bool rfc_empty_lits = P->with_dict();
-  HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, nullptr, nullptr, nullptr, false, s));
-  HIPCHK(launch_scan64(B->d_boff, B->d_nblk, n, 1, n, d_scratch, s));
-  HIPCHK(hipMemcpyAsync(WB.h_small, d_scratch + nt, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const uint64_t NB = WB.h_small[0];
+// zd_k_walk_chunks' count pass: d_nblk[i] = the blocks chunk i's walk keeps
+static int walk_count(zd_batch* B, hipStream_t s) {
+  HIPCHK(launch_walk_chunks(B->d_gather, ChunkList{B->d_src, B->d_size, B->d_off}, (uint32_t)B->n, B->P->with_dict(),
+                            B->d_nblk, nullptr, nullptr, nullptr, false, s));
+  return 0;
+}
+// zd_k_walk_chunks' fill pass over NB blocks in all, into WB.d_out (frames |
+// blocks).  h_boff: the blocks' places where the host summed them, uploaded
+// here with room made for the index's pinned copy; null: scanned in d_boff.
+static int walk_fill(zd_batch* B, DevWalkBufs& WB, uint64_t NB, const uint64_t* h_boff, hipStream_t s) {
+  const size_t n = B->n;
   if (NB >= (1ull << 32)) return ZD_E_OUT_OF_DOMAIN;
   const size_t fb = align_up(n * sizeof(HostFrame), 256), bytes = fb + NB * sizeof(HostBlock);
-  if (!grow_dev(WB.d_out, WB.cap_out, bytes)) return ZD_E_HIP;
+  if (!grow_dev(WB.d_out, WB.cap_out, bytes) || (h_boff && !grow_pinned(WB.h_out, WB.cap_h, bytes))) return ZD_E_HIP;
   WB.fb = fb;
   WB.bytes = bytes;
-  HIPCHK(launch_walk_chunks(B->d_gather, L, (uint32_t)n, rfc_empty_lits, B->d_nblk, B->d_boff, (HostFrame*)WB.d_out,
-                            (HostBlock*)(WB.d_out + fb), true, s));
-  if (packed) {
+  if (h_boff) HIPCHK(hipMemcpyAsync(B->d_boff, h_boff, 8 * n, hipMemcpyHostToDevice, s));
+  HIPCHK(launch_walk_chunks(B->d_gather, ChunkList{B->d_src, B->d_size, B->d_off}, (uint32_t)n, B->P->with_dict(),
+                            B->d_nblk, B->d_boff, (HostFrame*)WB.d_out, (HostBlock*)(WB.d_out + fb), true, s));
+  return 0;
+}
+
+// Host arrays: the walk with the blocks' places summed on the host, the index
+// back through the pinned copy, the capacity pass (zd_walk.h chunk_fit; bind
+// goes up with the descriptors) and the plan's parts.
+static int index_host(const BatchSpec& S, zd_batch* B, DevWalkBufs& WB, HostArrays& H) {
+  const size_t n = S.n;
+  const hipStream_t s = S.stream;
+  zd_plan* P = B->P;
+  H.bind.assign(n, 0);
+  P->place_out.assign(H.out, H.out + n);
+  P->place_cap = B->dst_cap;
+  std::lock_guard<std::mutex> lk(WB.m);
+  walk_bufs_on(WB, B->dev);
+  if (int r = walk_count(B, s)) return r;
+  std::vector<uint32_t> nblk(n);
+  HIPCHK(hipMemcpyAsync(nblk.data(), B->d_nblk, 4 * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::vector<uint64_t> boff(n);
+  uint64_t NB = 0;
+  for (size_t i = 0; i < n; i++) { boff[i] = NB; NB += nblk[i]; }
+  if (int r = walk_fill(B, WB, NB, boff.data(), s)) return r;
+  const HostFrame* cfr = nullptr;
+  const HostBlock* bl = nullptr;
+  if (int r = dev_walk_download(WB, s, &cfr, &bl)) return r;
+  HostFrame* fr = (HostFrame*)WB.h_out;
+  std::vector<const HostFrame*> kept(n);
+  for (size_t i = 0; i < n; i++) {
+    HostFrame& hf = fr[i];
+    kept[i] = &hf;
+    if (hf.d.kind == ZD_FRAME_ZSTD && hf.key == KEY_NONE) H.bind[i] = chunk_fit(hf, bl, S.dst_cap[i]);
+  }
+  std::vector<HostPart> parts;
+  parts_from(kept, bl, parts);
+  P->set_parts(std::move(parts));
+  return 0;
+}
+
+// Device arrays: the walk with the blocks' places scanned in d_boff; a packed
+// batch's own capacities and places (zd_k_batch_pack and one scan); a set's
+// IDs up, in `set_mem` with room for the plan's table and the used flags; then
+// the capacity pass, zd_k_batch_fit.  `in`: what build_plan_device takes over.
+static int index_device(const BatchSpec& S, zd_batch* B, DevWalkBufs& WB, DevPlanIn& in,
+                        std::unique_ptr<void, Free>& set_mem) {
+  const size_t n = S.n;
+  const hipStream_t s = S.stream;
+  const uint64_t nt = (n + 255) / 256;
+  if (int r = walk_count(B, s)) return r;
+  HIPCHK(launch_scan64(B->d_boff, B->d_nblk, n, 1, n, B->d_scratch, s));
+  HIPCHK(hipMemcpyAsync(WB.h_small, B->d_scratch + nt, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (int r = walk_fill(B, WB, WB.h_small[0], nullptr, s)) return r;
+  HostFrame* d_frames = (HostFrame*)WB.d_out;
+  const HostBlock* d_blocks = (const HostBlock*)(WB.d_out + WB.fb);
+  if (S.packed()) {
     // the chunks' reserves and places; the total comes back with the routing shape (build_plan_device's
     // first wait), in a pinned word the planner does not use
-    HIPCHK(launch_batch_pack((const HostFrame*)WB.d_out, (const HostBlock*)(WB.d_out + fb), B->d_flag, (uint32_t)n,
-                             align, B->d_cap, B->d_out, s));
-    HIPCHK(launch_scan64(B->d_out, nullptr, n, 1, n, d_scratch, s));
-    HIPCHK(hipMemcpyAsync(WB.h_small + 63, d_scratch + nt, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(launch_batch_pack(d_frames, d_blocks, B->d_flag, (uint32_t)n, S.align, B->d_cap, B->d_out, s));
+    HIPCHK(launch_scan64(B->d_out, nullptr, n, 1, n, B->d_scratch, s));
+    HIPCHK(hipMemcpyAsync(WB.h_small + 63, B->d_scratch + nt, 8, hipMemcpyDeviceToHost, s));
   }
-  // a dictionary set: its IDs go up, the used flags of its entries come back with the routing shape
-  struct Free { void operator()(void* p) const { if (p) (void)hipFree(p); } };
-  std::unique_ptr<void, Free> set_mem;
-  DevPlanIn in;
   in.place_out = B->d_out;
   in.place_cap = B->d_cap;
+  // a dictionary set: its IDs go up, the used flags of its entries come back with the routing shape
   const uint32_t* d_ids = nullptr;
   uint32_t nset = 0;
   if (B->dset) {
@@ -2860,26 +2750,95 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
     d_ids = ids;
     in.d_used = used;
   }
-  HIPCHK(launch_batch_fit((HostFrame*)WB.d_out, (const HostBlock*)(WB.d_out + fb), B->d_cap, B->d_flag, (uint32_t)n,
-                          B->d_bind, d_ids, nset, B->dset ? B->dset->fallback : -1, (uint8_t*)in.d_used, s));
+  HIPCHK(launch_batch_fit(d_frames, d_blocks, B->d_cap, B->d_flag, (uint32_t)n, B->d_bind, d_ids, nset,
+                          B->dset ? B->dset->fallback : -1, (uint8_t*)in.d_used, s));
+  return 0;
+}
+
+// Every batch is made here.  With device arrays the host reads back only a
+// few words a phase (the layout's totals, the block count, the routing shape
+// and a set's used flags, the plan's totals) and the frames' output offsets
+// and capacities.
+static int batch_create(const BatchSpec& S, zd_batch** out) {
+  // ---- argument checks: no HIP call before they are done ----
+  const size_t n = S.n;
+  if (!out || (S.flags & ZD_F_SKIPPABLE) || n >= (1ull << 31)) return ZD_E_INVALID_ARG;
+  if (n && (!S.src || !S.src_bytes || (!S.packed() && (!S.dst || !S.dst_cap)))) return ZD_E_INVALID_ARG;
+  if (S.packed() && (!S.on_device || S.dst || S.dst_cap)) return ZD_E_INVALID_ARG;
+  if (S.with_prefix() && (S.dict || S.dset || S.packed() || (n && (!S.prefix || !S.prefix_bytes))))
+    return ZD_E_INVALID_ARG;
+  if (!S.on_device)
+    if (int r = check_entries(S)) return r;
+
+  // ---- the batch; one of no chunks is done here ----
+  zd_batch* B = new (std::nothrow) zd_batch();
+  if (!B) return ZD_E_NO_MEMORY;
+  std::unique_ptr<zd_batch, Drop> hold(B);
+  B->n = n;
+  B->flags = S.flags;
+  B->device_built = S.on_device;
+  B->packed = S.packed();
+  B->info.nchunks = n;
+  B->info.device_built = S.on_device;
+  if (!n) { *out = hold.release(); return ZD_OK; }
+  HIPCHK(hipGetDevice(&B->dev));
+  if ((S.dict && S.dict->dev != B->dev) || (S.dset && S.dset->dev != B->dev)) return ZD_E_INVALID_ARG;
+  B->dict = S.dict;
+  B->dset = S.dset;
+  DevWalkBufs& WB = dev_walk_bufs();
+  std::unique_lock<std::mutex> lk(WB.m, std::defer_lock);   // (gather_device takes it, to the end of the call)
+  const auto t0 = std::chrono::steady_clock::now();
+
+  // ---- the gathered layout, the chunks' copies ----
+  HostArrays H;
+  if (int r = S.on_device ? gather_device(S, B, WB, lk) : gather_host(S, B, H)) return r;
+  const auto t1 = std::chrono::steady_clock::now();
+
+  // ---- the plan; zd_k_walk_chunks: count, the blocks' places, fill; the capacity pass ----
+  zd_plan* P = new (std::nothrow) zd_plan();
+  if (!P) return ZD_E_NO_MEMORY;
+  B->P = P;
+  P->flags = S.flags;
+  P->dict = B->dict;
+  P->dset = B->dset;
+  P->prefix = S.with_prefix();
+  if (P->prefix && S.on_device) {           // the checked entries, in the batch's own arrays
+    P->d_prefix_ptrs = B->d_pfx;
+    P->d_prefix_bytes = B->d_pfx_bytes;
+  } else if (P->prefix) {
+    P->prefix_ptrs.resize(n);
+    P->prefix_bytes.assign(S.prefix_bytes, S.prefix_bytes + n);
+    for (size_t i = 0; i < n; i++) {
+      P->prefix_ptrs[i] = S.prefix_bytes[i] ? (uint64_t)(uintptr_t)S.prefix[i] : 0;
+      B->info.prefix_bytes_total += S.prefix_bytes[i];
+    }
+  }
+  DevPlanIn in;                            // device arrays
+  std::unique_ptr<void, Free> set_mem;
+  if (int r = S.on_device ? index_device(S, B, WB, in, set_mem) : index_host(S, B, WB, H)) return r;
   P->index_status = 0;
   const auto t2 = std::chrono::steady_clock::now();
 
-  // ---- descriptors (zd_k_plan_*), placed at the chunks' destinations ----
-  if (int r = build_plan_device(P, WB, n, s, &in)) return r;
-  if (packed) B->out_bytes = WB.h_small[63];
+  // ---- descriptors (zd_k_plan_*, or the host planner), placed at the chunks' destinations ----
+  if (int r = S.on_device ? build_plan_device(P, WB, n, S.stream, &in) : build_plan_staged(P)) return r;
+  if (S.packed()) B->out_bytes = WB.h_small[63];
   P->index_stop = P->nframes;
-  P->info.src_bytes = total;
+  P->info.src_bytes = B->info.gathered_bytes;
   const auto t3 = std::chrono::steady_clock::now();
+
+  // ---- what the host planner leaves to upload; the dictionaries' tables; the second stream ----
+  if (!S.on_device)
+    if (int r = upload_desc(P)) return r;
   if (int r = upload_dict_tables(P)) return r;
+  if (!S.on_device) HIPCHK(hipMemcpy(B->d_bind, H.bind.data(), n, hipMemcpyHostToDevice));
   if (!aux_take(P)) return ZD_E_HIP;
   const auto t4 = std::chrono::steady_clock::now();
   zd_batch_info& I = B->info;
-  I.gathered_bytes = total;
   I.nblocks = P->info.nblocks;
   I.nsequences = P->info.nsequences;
   I.workspace_bytes = P->W.total + B->arr_bytes;
   I.executors = P->info.executors;
+  // (in.alloc_ns: the device planner's workspace allocation and small uploads count as upload)
   I.gather_ns = ns(t0, t1);
   I.walk_ns = ns(t1, t2);
   I.host_ns = ns(t2, t3) - std::min(in.alloc_ns, ns(t2, t3));
@@ -2888,42 +2847,77 @@ static int batch_create_device(const void* const* d_src, const uint64_t* d_src_b
   return ZD_OK;
 }
 
+int zd_batch_create(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst, const uint64_t* dst_cap,
+                    size_t nchunks, uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out) {
+  BatchSpec S{d_src, src_bytes, d_dst, dst_cap};
+  S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  if (!spec_dicts(S, dict, nullptr)) return ZD_E_INVALID_ARG;
+  return batch_create(S, out);
+}
+
+int zd_batch_create_prefix(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
+                           const uint64_t* dst_cap, const void* const* d_prefix, const uint64_t* prefix_bytes,
+                           size_t nchunks, uint32_t flags, void* stream, zd_batch** out) {
+  if (nchunks && (!d_prefix || !prefix_bytes)) return ZD_E_INVALID_ARG;
+  BatchSpec S{d_src, src_bytes, d_dst, dst_cap, d_prefix, prefix_bytes};
+  S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  return batch_create(S, out);
+}
+
+int zd_batch_create_dicts(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
+                          const uint64_t* dst_cap, size_t nchunks, uint32_t flags, const zd_dict_set* set, void* stream,
+                          zd_batch** out) {
+  BatchSpec S{d_src, src_bytes, d_dst, dst_cap};
+  S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  if (!set || !spec_dicts(S, nullptr, set)) return ZD_E_INVALID_ARG;
+  return batch_create(S, out);
+}
+
 int zd_batch_create_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
                            const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict, void* stream,
                            zd_batch** out) {
-  return batch_create_device(d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, nchunks, flags, dict, nullptr, stream, out);
+  BatchSpec S{d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap};
+  S.on_device = true; S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  if (!spec_dicts(S, dict, nullptr)) return ZD_E_INVALID_ARG;
+  return batch_create(S, out);
 }
 
 int zd_batch_create_device_prefix(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
                                   const uint64_t* d_dst_cap, const void* const* d_prefix_ptrs,
                                   const uint64_t* d_prefix_bytes, size_t nchunks, uint32_t flags, void* stream,
                                   zd_batch** out) {
-  return batch_create_device(d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, nchunks, flags, nullptr, nullptr, stream,
-                             out, 0, true, d_prefix_ptrs, d_prefix_bytes);
+  if (nchunks && (!d_prefix_ptrs || !d_prefix_bytes)) return ZD_E_INVALID_ARG;
+  BatchSpec S{d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, d_prefix_ptrs, d_prefix_bytes};
+  S.on_device = true; S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  return batch_create(S, out);
 }
 
 int zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
                                  const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict_set* set,
                                  void* stream, zd_batch** out) {
-  if (!set) return ZD_E_INVALID_ARG;
-  return batch_create_device(d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, nchunks, flags, nullptr, set, stream, out);
+  BatchSpec S{d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap};
+  S.on_device = true; S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  if (!set || !spec_dicts(S, nullptr, set)) return ZD_E_INVALID_ARG;
+  return batch_create(S, out);
 }
 
 static bool pack_align_ok(uint32_t align) { return align && align <= 4096 && !(align & (align - 1)); }
 
 int zd_batch_create_device_packed(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
                                   uint32_t align, uint32_t flags, const zd_dict* dict, void* stream, zd_batch** out) {
-  if (!pack_align_ok(align)) return ZD_E_INVALID_ARG;
-  return batch_create_device(d_src_ptrs, d_src_bytes, nullptr, nullptr, nchunks, flags, dict, nullptr, stream, out,
-                             align);
+  BatchSpec S{d_src_ptrs, d_src_bytes};
+  S.on_device = true; S.align = align; S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  if (!pack_align_ok(align) || !spec_dicts(S, dict, nullptr)) return ZD_E_INVALID_ARG;
+  return batch_create(S, out);
 }
 
 int zd_batch_create_device_packed_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
                                         uint32_t align, uint32_t flags, const zd_dict_set* set, void* stream,
                                         zd_batch** out) {
-  if (!set || !pack_align_ok(align)) return ZD_E_INVALID_ARG;
-  return batch_create_device(d_src_ptrs, d_src_bytes, nullptr, nullptr, nchunks, flags, nullptr, set, stream, out,
-                             align);
+  BatchSpec S{d_src_ptrs, d_src_bytes};
+  S.on_device = true; S.align = align; S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  if (!set || !pack_align_ok(align) || !spec_dicts(S, nullptr, set)) return ZD_E_INVALID_ARG;
+  return batch_create(S, out);
 }
 
 int zd_batch_output_layout(const zd_batch* B, uint64_t* out_bytes, const uint64_t** d_offset, const uint64_t** d_cap) {
@@ -3035,12 +3029,16 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
         dst[k] = (void*)(uintptr_t)B->dst[i];
         dc[k] = B->dst_cap[i];
       }
-      const uint32_t flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_J_ONE_ROUND)) | ZD_F_FRAME_SERIAL;
-      zd_dict dh{B->dict};
-      zd_dict_set sh{B->dset};
+      // (no prefixes to hand on: plan_ctx turns K4J off for every dictionary,
+      // set and prefix plan, so such a batch never has n_jframes)
+      BatchSpec S{src.data(), sz.data(), dst.data(), dc.data()};
+      S.n = m;
+      S.flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_J_ONE_ROUND)) | ZD_F_FRAME_SERIAL;
+      S.dict = B->dict;
+      S.dset = B->dset;
+      S.stream = s;
       zd_batch* Q = nullptr;
-      int r = batch_create(src.data(), sz.data(), dst.data(), dc.data(), m, flags, B->dict ? &dh : nullptr,
-                           B->dset ? &sh : nullptr, s, &Q);
+      int r = batch_create(S, &Q);
       if (r) return r;
       std::vector<int32_t> st2(m);
       std::vector<uint64_t> ln2(m);

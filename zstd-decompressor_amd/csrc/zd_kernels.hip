@@ -6809,13 +6809,7 @@ __global__ __launch_bounds__(256) void zd_k_batch_fit(HostFrame* frames, const H
     hf.status = code;
     hf.key = make_key(PH_LIMIT, 0, 0, 0, code);
   } else if (hf.d.kind == ZD_FRAME_ZSTD && hf.key == KEY_NONE) {
-    const uint64_t bound = frame_bound(hf, blocks);
-    const bool usable = hf.d.content_size != UINT64_MAX && hf.d.content_size <= bound;
-    if (usable && hf.d.content_size > cap[i]) {
-      hf.status = ZD_E_DST_TOO_SMALL;
-      hf.key = make_key(PH_LIMIT, 0, 0, 0, ZD_E_DST_TOO_SMALL);
-    }
-    b = !usable && cap[i] < bound;
+    b = chunk_fit(hf, blocks, cap[i]);
   }
   bind[i] = b;
   if (used && hf.d.kind == ZD_FRAME_ZSTD) {

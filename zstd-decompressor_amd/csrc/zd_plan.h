@@ -416,5 +416,56 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   c.frames++;
 }
 
+// A batch's per-chunk arrays (zd_host.cpp zd_batch::d_arr): one allocation,
+// carved here into byte offsets, array after array (n entries each unless
+// said otherwise).  Host arrays (zd_batch_create): src | size | off | out |
+// pieces (npieces GatherPiece slots of 8 bytes) are the head the host uploads,
+// [head_bytes, total) is zeroed and written by the device.  Device arrays
+// (zd_batch_create_device): piece0 follows off (BatchArrays: the layout scans
+// the two as adjacent columns), cap and flag are the chunks' capacities and
+// CHUNK_* flags, scratch the scans' 2 * (tiles + 1) + 1 words (tiles of 256
+// chunks), res the four words that come back, and a prefix batch keeps the
+// checked prefix addresses and sizes after everything else.  ABSENT: an
+// array the kind of batch does not have.
+struct BatchCarve {
+  static constexpr uint64_t ABSENT = UINT64_MAX;
+  uint64_t src = 0, size = 0, off = 0, out = 0;           // u64
+  uint64_t boff = 0, len = 0, hash = 0;                   // u64
+  uint64_t status = 0, nblk = 0;                          // i32, u32
+  uint64_t bind = 0;                                      // u8
+  uint64_t pieces = ABSENT, head_bytes = 0;               // host arrays
+  uint64_t piece0 = ABSENT, cap = ABSENT;                 // device arrays: u64
+  uint64_t flag = ABSENT;                                 //   u8
+  uint64_t scratch = ABSENT, res = ABSENT;                //   u64 words
+  uint64_t pfx = ABSENT, pfx_bytes = ABSENT;              //   u64, a prefix batch
+  uint64_t scratch_words = 0;
+  uint64_t total = 0;
+
+  void carve(uint64_t n, bool on_device, uint64_t npieces, bool prefixes) {
+    uint64_t o = 0;
+    auto take = [&o](uint64_t bytes) { const uint64_t at = o; o += bytes; return at; };
+    src = take(8 * n); size = take(8 * n); off = take(8 * n);
+    if (on_device) {
+      piece0 = take(8 * n); out = take(8 * n); cap = take(8 * n);
+    } else {
+      out = take(8 * n); pieces = take(8 * npieces);
+      head_bytes = o;
+    }
+    boff = take(8 * n); len = take(8 * n); hash = take(8 * n);
+    status = take(4 * n); nblk = take(4 * n);
+    bind = take(n);
+    if (on_device) {
+      flag = take(n);
+      o = plan_align(o, 8);
+      scratch_words = 2 * ((n + 255) / 256 + 1) + 1;
+      scratch = take(8 * scratch_words); res = take(8 * 4);
+      if (prefixes) { pfx = take(8 * n); pfx_bytes = take(8 * n); }
+    } else {
+      o = bind + plan_align(n, 8);
+    }
+    total = o;
+  }
+};
+
 
 }  // namespace zd

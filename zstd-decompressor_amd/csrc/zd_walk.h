@@ -390,6 +390,22 @@ ZD_HD inline uint64_t chunk_reserve(const HostFrame& hf, uint64_t bound, uint8_t
   *exact = usable ? 1 : 0;
   return usable ? hf.d.content_size : bound;
 }
+// The capacity pass of every batch, for an indexed zstd frame (kind
+// ZD_FRAME_ZSTD, key KEY_NONE) and its chunk's capacity: a usable
+// Frame_Content_Size above the capacity is ZD_E_DST_TOO_SMALL here (status and
+// key), and nothing of the chunk runs.  Returns the chunk's bind flag: the
+// capacity is below what the plan reserves for a frame without a usable one.
+// (`cap` by reference: zd_k_batch_fit hands in its array's entry, read where
+// it is used.)
+ZD_HD inline bool chunk_fit(HostFrame& hf, const HostBlock* blocks, const uint64_t& cap) {
+  const uint64_t bound = frame_bound(hf, blocks);
+  const bool usable = hf.d.content_size != UINT64_MAX && hf.d.content_size <= bound;
+  if (usable && hf.d.content_size > cap) {
+    hf.status = ZD_E_DST_TOO_SMALL;
+    hf.key = make_key(PH_LIMIT, 0, 0, 0, ZD_E_DST_TOO_SMALL);
+  }
+  return !usable && cap < bound;
+}
 
 // A block sink that keeps the frame's bound and block count and no block:
 // index_chunk over it gives a chunk's reserve with no index stored (the

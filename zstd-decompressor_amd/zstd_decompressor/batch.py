@@ -266,24 +266,26 @@ def _u64_array(values, n: int):
     return (C.c_uint64 * n).from_buffer(a) if n else (C.c_uint64 * 1)()
 
 
-def _device_arrays(arrs, nchunks):
+def _device_arrays(arrs, nchunks, lists=True):
     """(n, device addresses, tensors to keep) of per-chunk arrays given as
     contiguous 1-D int64 / uint64 device tensors, device addresses (with
-    nchunks), or Python lists, which are uploaded as one int64 tensor each (the
-    upload is waited for, so the arrays are readable on any stream)."""
-    import torch
+    nchunks), or (unless lists=False) Python lists, which are uploaded as one
+    int64 tensor each (the upload is waited for, so the arrays are readable on
+    any stream)."""
     n, addr, keep, uploaded = nchunks, [], [], False
     for a in arrs:
         if isinstance(a, int):
             addr.append(a)
             continue
-        if isinstance(a, (list, tuple)):
+        import torch
+        if lists and isinstance(a, (list, tuple)):
             a = torch.tensor([int(v or 0) for v in a], dtype=torch.int64,
                              device=torch.device("cuda", torch.cuda.current_device()))
             uploaded = True
         if not (isinstance(a, torch.Tensor) and a.is_cuda and a.is_contiguous() and a.dim() == 1
                 and a.dtype in (torch.int64, torch.uint64)):
-            raise ValueError("contiguous 1-D int64 / uint64 device tensors, device addresses or lists required")
+            raise ValueError("contiguous 1-D int64 / uint64 device tensors%s required"
+                             % (", device addresses or lists" if lists else ", or device addresses,"))
         if n is None:
             n = a.numel()
         if a.numel() != n:
@@ -328,6 +330,17 @@ def _batch_info(h):
     return info
 
 
+def _with_dictionary(name, dictionary):
+    """(entry point, handle) for a batch made with `dictionary`: `name` with
+    a Dictionary's handle or None, name + "_dicts" with a DictionarySet's.  A
+    closed dictionary or set is a ValueError."""
+    if dictionary is None:
+        return name, None
+    if not getattr(dictionary, "_h", None):
+        raise ValueError("the %s is closed" % type(dictionary).__name__)
+    return (name + "_dicts" if isinstance(dictionary, DictionarySet) else name), dictionary._h
+
+
 class Batch:
     """zd_batch: N independently compressed chunks at N device addresses, each
     decoded into its own device buffer with its own status (dictionary: a
@@ -349,30 +362,26 @@ class Batch:
         n = len(src_ptrs)
         if not (len(src_sizes) == len(dst_ptrs) == len(dst_caps) == n):
             raise ValueError("src_ptrs, src_sizes, dst_ptrs and dst_caps differ in length")
-        if dictionary is not None and not getattr(dictionary, "_h", None):
-            raise ValueError("the %s is closed" % type(dictionary).__name__)
+        name, dh = _with_dictionary("zd_batch_create", dictionary)
         if prefixes is not None and dictionary is not None:
             raise ValueError("prefixes= and dictionary= exclude one another")
         sp, ss, dp, dc = (_u64_array(v, n) for v in (src_ptrs, src_sizes, dst_ptrs, dst_caps))
         vpp = C.POINTER(C.c_void_p)
-        h = C.c_void_p()
         if prefixes is not None:
             pptrs, psizes = prefixes
             if not (len(pptrs) == len(psizes) == n):
                 raise ValueError("the prefixes and the chunks differ in length")
             pp, ps = _u64_array(pptrs, n), _u64_array(psizes, n)
-            _lib.check(_lib.lib().zd_batch_create_prefix(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, C.cast(pp, vpp), ps,
-                                                         n, flags, C.c_void_p(stream), C.byref(h)),
-                       "zd_batch_create_prefix")
-        elif isinstance(dictionary, DictionarySet):
-            _lib.check(_lib.lib().zd_batch_create_dicts(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, n, flags,
-                                                        dictionary._h, C.c_void_p(stream), C.byref(h)),
-                       "zd_batch_create_dicts")
+            self._create("zd_batch_create_prefix", n, C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, C.cast(pp, vpp), ps,
+                         n, flags, C.c_void_p(stream))
         else:
-            _lib.check(_lib.lib().zd_batch_create(C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, n, flags,
-                                                  dictionary._h if dictionary else None, C.c_void_p(stream),
-                                                  C.byref(h)),
-                       "zd_batch_create")
+            self._create(name, n, C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, n, flags, dh, C.c_void_p(stream))
+
+    def _create(self, name, n, *args):
+        """Calls the zd_batch_create* entry point `name` (the handle it
+        returns is its last argument, added here) and takes the batch over."""
+        h = C.c_void_p()
+        _lib.check(getattr(_lib.lib(), name)(*args, C.byref(h)), name)
         self._h = h
         self.nchunks = n
         self.info = _batch_info(h)
@@ -398,45 +407,14 @@ class Batch:
         arrs = (src_ptrs, src_sizes, dst_ptrs, dst_caps) + (tuple(prefixes) if prefixes is not None else ())
         if len(arrs) not in (4, 6):
             raise ValueError("prefixes is a pair (ptrs, sizes)")
-        n, addr, keep = nchunks, [], []
-        for a in arrs:
-            if isinstance(a, int):
-                addr.append(a)
-                continue
-            import torch
-            if not (isinstance(a, torch.Tensor) and a.is_cuda and a.is_contiguous() and a.dim() == 1
-                    and a.dtype in (torch.int64, torch.uint64)):
-                raise ValueError("contiguous 1-D int64 / uint64 device tensors, or device addresses, required")
-            if n is None:
-                n = a.numel()
-            if a.numel() != n:
-                raise ValueError("the arrays and nchunks differ in length")
-            addr.append(a.data_ptr() if n else 0)
-            keep.append(a)
-        if n is None:
-            raise ValueError("nchunks is required when every array is a raw address")
-        if dictionary is not None and not getattr(dictionary, "_h", None):
-            raise ValueError("the %s is closed" % type(dictionary).__name__)
+        n, addr, keep = _device_arrays(arrs, nchunks, lists=False)
+        name, dh = _with_dictionary("zd_batch_create_device", dictionary)
         self = cls.__new__(cls)
-        h = C.c_void_p()
-        sp, ss, dp, dc = (C.c_void_p(a) for a in addr[:4])
+        ptrs = [C.c_void_p(a) for a in addr]
         if prefixes is not None:
-            _lib.check(_lib.lib().zd_batch_create_device_prefix(sp, ss, dp, dc, C.c_void_p(addr[4]), C.c_void_p(addr[5]),
-                                                                n, flags, C.c_void_p(stream), C.byref(h)),
-                       "zd_batch_create_device_prefix")
-        elif isinstance(dictionary, DictionarySet):
-            _lib.check(_lib.lib().zd_batch_create_device_dicts(sp, ss, dp, dc, n, flags, dictionary._h,
-                                                               C.c_void_p(stream), C.byref(h)),
-                       "zd_batch_create_device_dicts")
+            self._create("zd_batch_create_device_prefix", n, *ptrs, n, flags, C.c_void_p(stream))
         else:
-            _lib.check(_lib.lib().zd_batch_create_device(sp, ss, dp, dc, n, flags,
-                                                         dictionary._h if dictionary else None, C.c_void_p(stream),
-                                                         C.byref(h)),
-                       "zd_batch_create_device")
-        del keep
-        self._h = h
-        self.nchunks = n
-        self.info = _batch_info(h)
+            self._create(name, n, *ptrs, n, flags, dh, C.c_void_p(stream))
         return self
 
     @classmethod
@@ -452,26 +430,11 @@ class Batch:
         buffer.  A frame without a usable Frame_Content_Size gets its bound, so
         there is slack after it: results() tells the lengths."""
         n, addr, keep = _device_arrays((src_ptrs, src_sizes), nchunks)
-        if dictionary is not None and not getattr(dictionary, "_h", None):
-            raise ValueError("the %s is closed" % type(dictionary).__name__)
+        name, dh = _with_dictionary("zd_batch_create_device_packed", dictionary)
         self = cls.__new__(cls)
-        h = C.c_void_p()
-        sp, ss = (C.c_void_p(a) for a in addr)
-        if isinstance(dictionary, DictionarySet):
-            _lib.check(_lib.lib().zd_batch_create_device_packed_dicts(sp, ss, n, align, flags, dictionary._h,
-                                                                      C.c_void_p(stream), C.byref(h)),
-                       "zd_batch_create_device_packed_dicts")
-        else:
-            _lib.check(_lib.lib().zd_batch_create_device_packed(sp, ss, n, align, flags,
-                                                                dictionary._h if dictionary else None,
-                                                                C.c_void_p(stream), C.byref(h)),
-                       "zd_batch_create_device_packed")
-        del keep
-        self._h = h
-        self.nchunks = n
-        self.info = _batch_info(h)
+        self._create(name, n, C.c_void_p(addr[0]), C.c_void_p(addr[1]), n, align, flags, dh, C.c_void_p(stream))
         ob = C.c_uint64()
-        _lib.check(_lib.lib().zd_batch_output_layout(h, C.byref(ob), None, None), "zd_batch_output_layout")
+        _lib.check(_lib.lib().zd_batch_output_layout(self._h, C.byref(ob), None, None), "zd_batch_output_layout")
         self.out_bytes = ob.value
         return self
 
