@@ -72,7 +72,8 @@ extern "C" {
 #define ZD_E_INVALID_ARG     (-93)
 #define ZD_E_HIP             (-94) /* a HIP runtime call failed */
 #define ZD_E_NO_MEMORY       (-95)
-#define ZD_E_NOT_DECODED     (-96) /* frame skipped: an earlier frame failed (FrameIterator stops, frame.rs:94-99) */
+#define ZD_E_NOT_DECODED     (-96) /* frame skipped: an earlier frame failed (FrameIterator stops, frame.rs:94-99);
+                                      in a chain batch: a chunk whose parent, or an ancestor further up, failed */
 #define ZD_E_COMM            (-97) /* an RCCL call failed, or RCCL is not loadable */
 #define ZD_E_DICT_CORRUPTED  (-98) /* zd_dict_create: a formatted dictionary truncated before its content, with
                                       a repeat offset of 0 or past the content, or without content */
@@ -516,8 +517,9 @@ typedef struct zd_batch_info {
  * zstd frame, with any number of skippable frames (skipped, never output)
  * before and after it; a chunk of zero bytes or of skippable frames only is
  * ZD_OK with length 0.  Chunks are independent: every chunk gets its own
- * status, no chunk's failure touches another (ZD_E_NOT_DECODED never appears)
- * and a failing chunk's length is 0:
+ * status, no chunk's failure touches another (ZD_E_NOT_DECODED never appears,
+ * but in a chain batch, zd_batch_create_chain, for a chunk behind a failed
+ * ancestor) and a failing chunk's length is 0:
  *   the walk's own code        the chunk is not consumed entirely that way
  *                              (ZD_E_UNRECOGNIZED_MAGIC, ZD_E_NOT_ENOUGH_BYTES,
  *                              ...: trailing bytes, a truncated frame)
@@ -641,10 +643,10 @@ int  zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t*
  * prefix_bytes[i] > 0; a prefix range that wraps; a prefix range that overlaps
  * a destination range.  nchunks == 0 is ZD_OK.
  * Limits (not in this interface): no packed prefix batches; prefixes cannot be
- * re-pointed after creation; a chunk's prefix cannot be another chunk's output
- * of the SAME launch (chunks run concurrently); no prefixes on the LDS-resident,
- * block-parallel or fused executors; none in zd_plan_*, the sharded calls or
- * zd_context. */
+ * re-pointed after creation; no prefixes on the LDS-resident, block-parallel or
+ * fused executors; none in zd_plan_*, the sharded calls or zd_context.  (A
+ * chunk whose prefix is another chunk's output of the same launch: a chain
+ * batch, zd_batch_create_chain.) */
 int  zd_batch_create_prefix(const void* const* d_src, const uint64_t* src_bytes,
                             void* const* d_dst, const uint64_t* dst_cap,
                             const void* const* d_prefix, const uint64_t* prefix_bytes,
@@ -661,6 +663,81 @@ int  zd_batch_create_device_prefix(const void* const* d_src_ptrs, const uint64_t
                                    void* const* d_dst_ptrs, const uint64_t* d_dst_cap,
                                    const void* const* d_prefix_ptrs, const uint64_t* d_prefix_bytes,
                                    size_t nchunks, uint32_t flags, void* stream, zd_batch** out);
+/* Delta chains: a prefix batch in which a chunk's prefix may be ANOTHER CHUNK'S
+ * OUTPUT OF THE SAME LAUNCH -- page versions v1 <- v2 <- v3, a record and its
+ * patches, a shard patched every step -- decoded by one batch instead of one
+ * batch per link.  The seven arrays are host arrays of nchunks entries; the
+ * first six are zd_batch_create_prefix's.
+ *  - parent[i] == -1: chunk i is exactly a chunk of a prefix batch, its prefix
+ *    d_prefix[i] / prefix_bytes[i] (0 bytes: none).  d_prefix and prefix_bytes
+ *    may BOTH be NULL: no external prefix anywhere.  parent must not be NULL
+ *    when nchunks > 0.
+ *  - parent[i] == j, j in [0, nchunks), j != i: chunk i's prefix is chunk j's
+ *    decoded output of the same launch, at d_dst[j]; its size is j's
+ *    Frame_Content_Size; prefix_bytes[i] must be 0.  The order of the chunks is
+ *    free (a child may come before its parent) and many children may share a
+ *    parent.  A chunk's LEVEL is the number of its in-batch ancestors, at most
+ *    ZD_CHAIN_MAX_DEPTH.
+ *  - How it runs.  Tables, literals and sequence chains of every chunk run once,
+ *    together, as in a prefix batch: only execution reads a prefix.  The
+ *    streaming executor (zd_k_execute_chain) is then launched once per level, in
+ *    level order on the stream, so a parent is complete before its children
+ *    start: no workgroup ever waits for another.
+ *  - Statuses.  A chunk whose parent's final status is not ZD_OK is
+ *    ZD_E_NOT_DECODED with length 0 -- final includes ZD_E_CHECKSUM_WRONG from
+ *    ZD_F_VERIFY_CHECKSUM and a parent whose decoded length is not the size the
+ *    child was planned with -- and so, transitively, is every chunk behind it.
+ *    No prefix byte is read for such a chunk (with ZD_F_VERIFY_CHECKSUM a child
+ *    has run against its parent's bytes, inside the parent's buffer, before the
+ *    parent's checksum is known); its leading raw / RLE blocks may have been
+ *    copied into its own destination already: nothing outside the destination
+ *    ranges is ever written.  zd_batch_device_checksums' entries of such a
+ *    chunk are unspecified.  A chunk whose parent's frame carries no
+ *    Frame_Content_Size is ZD_E_OUT_OF_DOMAIN at creation (the size is needed
+ *    to plan it); the parent is unaffected.  A parent that is an empty chunk or
+ *    holds skippable frames only (ZD_OK, length 0) gives its child a prefix of
+ *    0 bytes: the child decodes as a plain chunk.  Prefix size plus capacity
+ *    above 0x7FFF0000 is ZD_E_OUT_OF_DOMAIN for that chunk, as in a prefix
+ *    batch.
+ *  - ZD_E_INVALID_ARG for the whole call, before any HIP call: what
+ *    zd_batch_create_prefix refuses (its prefix-overlaps-destination rule for
+ *    the external prefixes only; exactly one of d_prefix / prefix_bytes NULL);
+ *    a parent outside [-1, nchunks); parent[i] == i; a cycle; a chunk with more
+ *    than ZD_CHAIN_MAX_DEPTH ancestors; prefix_bytes[i] != 0 on a chunk with a
+ *    parent.  nchunks == 0 is ZD_OK.
+ * Everything else is a prefix batch's: the streaming executor only, no
+ * dictionary or set, not packed, ZD_F_SKIPPABLE refused, the sources gathered
+ * at creation, zd_batch_decode_async free of allocation and host
+ * synchronisation, capturable and re-launchable; every zd_batch_* call works on
+ * the result (zd_batch_info.prefix_bytes_total counts the external prefixes).
+ * Limits (not in this interface): no packed chain batches, no re-pointing, no
+ * chains through dictionaries, none in zd_plan_*, the sharded calls or
+ * zd_context. */
+#define ZD_CHAIN_MAX_DEPTH 255   /* in-batch ancestors a chunk may have: levels 0..255 */
+int  zd_batch_create_chain(const void* const* d_src, const uint64_t* src_bytes,
+                           void* const* d_dst, const uint64_t* dst_cap,
+                           const void* const* d_prefix, const uint64_t* prefix_bytes,
+                           const int64_t* parent, size_t nchunks, uint32_t flags,
+                           void* stream, zd_batch** out);
+/* zd_batch_create_chain for a chunk table on the device: the seven arrays are
+ * DEVICE arrays of nchunks entries (d_prefix_ptrs and d_prefix_bytes may both
+ * be NULL), under zd_batch_create_device_prefix's terms and with its host
+ * waits, none more.  What the host-array call refuses the call for is a
+ * per-chunk outcome: a parent outside [-1, nchunks), a chunk that names itself,
+ * a prefix size on a chunk with a parent, and a chunk that reaches no root
+ * within ZD_CHAIN_MAX_DEPTH hops -- on a cycle, behind one, or deeper than the
+ * limit -- make that chunk ZD_E_INVALID_ARG (length 0); the chunks behind a
+ * refused chunk that are not refused themselves are ZD_E_NOT_DECODED. */
+int  zd_batch_create_device_chain(const void* const* d_src_ptrs, const uint64_t* d_src_bytes,
+                                  void* const* d_dst_ptrs, const uint64_t* d_dst_cap,
+                                  const void* const* d_prefix_ptrs, const uint64_t* d_prefix_bytes,
+                                  const int64_t* d_parent, size_t nchunks, uint32_t flags,
+                                  void* stream, zd_batch** out);
+/* A chain batch's shape: the number of levels (1 when no chunk has a parent, or
+ * the batch has no chunks) = the executor launches of a decode at most, and the
+ * number of chunks with a parent.  Either pointer may be NULL.  ZD_E_INVALID_ARG
+ * for a NULL batch or one that was not made by a chain call. */
+int  zd_batch_chain_info(const zd_batch* batch, uint32_t* levels, uint64_t* links);
 /* What chunks need of their destinations, asked on the device: chunk i is the
  * d_src_bytes[i] bytes at d_src_ptrs[i], as in zd_batch_create_device.  All
  * five arrays are DEVICE arrays of nchunks entries; d_status and d_exact may be

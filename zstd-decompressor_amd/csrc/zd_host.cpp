@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/zd.h"
+#include "zd_chain.h"
 #include "zd_common.h"
 #include "zd_internal.h"
 #include "zd_launch.h"
@@ -146,6 +147,13 @@ struct zd_plan {
   bool prefix = false;
   std::vector<uint64_t> prefix_ptrs, prefix_bytes;
   const uint64_t *d_prefix_ptrs = nullptr, *d_prefix_bytes = nullptr;
+  // a chain batch (zd_batch_create_chain; a prefix batch in everything above):
+  // the frames grouped by level and each frame's parent, device arrays the
+  // batch owns, and the levels' frame counts (K4_CHAIN: one launch a level)
+  bool chain = false;
+  const uint32_t* d_chain_order = nullptr;
+  const int32_t* d_chain_parent = nullptr;
+  std::vector<uint32_t> chain_count;
   bool with_dict() const { return dict != nullptr || dset != nullptr || prefix; }
   std::vector<HostPart> parts;          // the host walk's frames, in input order
   std::vector<size_t> part_f0;          // plan frame index of each part's first frame
@@ -1094,6 +1102,7 @@ struct DevWalkBufs {                      // device and pinned buffers, kept bet
   size_t cap_fo = 0;
   PlanShape* d_shape = nullptr;
   uint64_t* h_small = nullptr;           // pinned: shape, totals
+  uint32_t* h_chain = nullptr;           // pinned: a chain batch's level counts, cursors and links (BatchCarve::lcount)
 };
 DevWalkBufs& dev_walk_bufs() {
   static DevWalkBufs* b = new DevWalkBufs();
@@ -1908,8 +1917,15 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
   // the route, resolved every launch (profiling may have been switched since
   // the last one); the rest of `a` is what the route's launches need
   const LaunchIn in{P->cus, P->n_frames, P->n_tables, P->n_huf, P->n_seq, P->flags, P->fused,
-                    P->prefix ? K4_PREFIX : P->dset ? K4_DICT_SET : P->dict ? K4_DICT : K4_PLAIN, P->profile ? 1 : P->profile_dom ? 2 : 0};
+                    P->chain ? K4_CHAIN : P->prefix ? K4_PREFIX : P->dset ? K4_DICT_SET : P->dict ? K4_DICT : K4_PLAIN,
+                    P->profile ? 1 : P->profile_dom ? 2 : 0};
   const LaunchRoute R = a.route = launch_route(in, route_env());
+  if (P->chain) {
+    a.chain_order = P->d_chain_order;
+    a.chain_parent = P->d_chain_parent;
+    a.chain_count = P->chain_count.data();
+    a.chain_levels = (uint32_t)P->chain_count.size();
+  }
   // (every plan has its second stream, aux_take, and a profiled one its events, zd_plan_set_profiling)
   if (((R.fork || R.k1_fork) && !P->aux) || (R.profiling && !P->ev_made)) return ZD_E_HIP;
   a.aux = P->aux; a.fork = P->fork; a.join = P->join;
@@ -2449,6 +2465,15 @@ struct zd_batch {
   // a prefix batch made from device arrays (zd_batch_create_device_prefix):
   // the checked prefix addresses and sizes, in d_arr
   uint64_t *d_pfx = nullptr, *d_pfx_bytes = nullptr;
+  // a chain batch (zd_batch_create_chain): the chunks' checked parents, the
+  // chunks grouped by level and (device arrays) the kernels' counters and
+  // levels, in d_arr; the levels' counts up to the last one in use, the links
+  bool chain = false;
+  int32_t* d_par = nullptr;
+  uint32_t *d_order = nullptr, *d_lcount = nullptr;
+  uint8_t* d_lvl = nullptr;
+  std::vector<uint32_t> chain_count;
+  uint64_t chain_links = 0;
   int host_arrays() {
     if (!device_built || goff.size() == n) return 0;
     std::vector<uint64_t> o(n), z(n), d(n), c(n);
@@ -2490,6 +2515,7 @@ struct BatchSpec {
   const uint64_t* dst_cap = nullptr;
   const void* const* prefix = nullptr;     // (both null: no prefixes)
   const uint64_t* prefix_bytes = nullptr;
+  const int64_t* parent = nullptr;         // a chain batch (the prefix arrays may then both be null); else null
   bool on_device = false;
   size_t n = 0;
   uint32_t flags = 0;
@@ -2498,7 +2524,8 @@ struct BatchSpec {
   std::shared_ptr<DictSetData> dset;
   hipStream_t stream = nullptr;
   bool packed() const { return align != 0; }
-  bool with_prefix() const { return prefix || prefix_bytes; }
+  bool chain = false;                      // made by a chain call (parent null only with n == 0)
+  bool with_prefix() const { return prefix || prefix_bytes || chain; }
 };
 // (an entry point's handles: false for one without data)
 static bool spec_dicts(BatchSpec& S, const zd_dict* dict, const zd_dict_set* set) {
@@ -2527,6 +2554,8 @@ static int batch_arrays(zd_batch* B, const BatchCarve& C) {
   B->d_flag = at(C.flag);
   B->d_scratch = (uint64_t*)at(C.scratch); B->d_res = (uint64_t*)at(C.res);
   B->d_pfx = (uint64_t*)at(C.pfx); B->d_pfx_bytes = (uint64_t*)at(C.pfx_bytes);
+  B->d_par = (int32_t*)at(C.par); B->d_order = (uint32_t*)at(C.order); B->d_lcount = (uint32_t*)at(C.lcount);
+  B->d_lvl = at(C.lvl);
   return 0;
 }
 
@@ -2546,8 +2575,11 @@ static int check_entries(const BatchSpec& S) {
   // a prefix is read while the destinations are written: no prefix range may
   // meet one (the sorted destinations are disjoint, so of those that start
   // below the prefix's end the last one reaches furthest)
-  for (size_t i = 0; S.with_prefix() && i < S.n; i++) {
+  // (a chain batch: the external prefixes only -- a chained chunk's prefix IS
+  // its parent's destination, complete before the chunk's level starts)
+  for (size_t i = 0; S.prefix && i < S.n; i++) {
     const uint64_t a = (uint64_t)(uintptr_t)S.prefix[i], z = S.prefix_bytes[i];
+    if (S.chain && S.parent[i] != -1 && z) return ZD_E_INVALID_ARG;
     if ((!a && z) || a + z < a) return ZD_E_INVALID_ARG;
     if (!z) continue;
     auto it = std::lower_bound(ranges.begin(), ranges.end(), std::pair<uint64_t, uint64_t>{a + z, 0});
@@ -2561,7 +2593,27 @@ struct HostArrays {
   std::vector<uint64_t> head;        // d_arr's uploaded head (kept to the end of the call)
   const uint64_t* out = nullptr;     //   its out column: the plan's place_out
   std::vector<uint8_t> bind;         // the capacity pass's flags, uploaded after the descriptors
+  std::vector<uint32_t> chain;       // a chain batch: the parents (i32) | the chunks by level, one upload behind the head
 };
+
+// Host arrays of a chain batch: every parent entry is checked here (zd_chain.h:
+// an index outside [-1, n), a chunk that names itself, a cycle, more than
+// ZD_CHAIN_MAX_DEPTH ancestors fail the call), the chunks are grouped by level.
+static int chain_host(const BatchSpec& S, zd_batch* B, HostArrays& H) {
+  const size_t n = S.n;
+  std::vector<int32_t> level(n);
+  uint32_t count[CHAIN_LEVELS];
+  H.chain.resize(2 * n);
+  if (chain_order(S.parent, n, level.data(), H.chain.data() + n, count)) return ZD_E_INVALID_ARG;
+  uint32_t levels = 1;
+  for (size_t i = 0; i < n; i++) {
+    H.chain[i] = (uint32_t)(int32_t)S.parent[i];
+    B->chain_links += S.parent[i] >= 0;
+    levels = std::max(levels, (uint32_t)level[i] + 1);
+  }
+  B->chain_count.assign(count, count + levels);
+  return 0;
+}
 
 // Host arrays: the gathered layout and zd_k_gather's pieces, made here and
 // uploaded as d_arr's head; then the gather.  info.gathered_bytes is set.
@@ -2585,7 +2637,7 @@ static int gather_host(const BatchSpec& S, zd_batch* B, HostArrays& H) {
   if (npieces * (COPY_PIECE / 4096) >= (1ull << 31)) return ZD_E_OUT_OF_DOMAIN;   // zd_k_gather's grid
   B->outbase = (uint8_t*)(uintptr_t)lowest;
   BatchCarve C;
-  C.carve(n, false, npieces, false);
+  C.carve(n, false, npieces, false, S.chain);
   std::vector<uint64_t>& head = H.head;
   head.resize(C.head_bytes / 8);
   uint64_t *h_src = head.data() + C.src / 8, *h_size = head.data() + C.size / 8, *h_off = head.data() + C.off / 8,
@@ -2610,6 +2662,10 @@ static int gather_host(const BatchSpec& S, zd_batch* B, HostArrays& H) {
   HIPCHK(ws_alloc(B->dev, std::max<uint64_t>(total, 16), &B->d_gather, &B->gather_alloc));
   HIPCHK(hipMemcpyAsync(B->d_arr, head.data(), C.head_bytes, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(B->d_arr + C.head_bytes, 0, C.total - C.head_bytes, s));
+  if (S.chain) {                             // (par | order: adjacent in d_arr)
+    if ((uint8_t*)B->d_order != (uint8_t*)B->d_par + 4 * n) return ZD_E_INVALID_ARG;
+    HIPCHK(hipMemcpyAsync(B->d_par, H.chain.data(), 8 * n, hipMemcpyHostToDevice, s));
+  }
   HIPCHK(launch_gather(ChunkList{B->d_src, B->d_size, B->d_off}, B->d_gather, B->d_pieces, npieces, s));
   HIPCHK(hipStreamSynchronize(s));
   B->info.gathered_bytes = total;
@@ -2625,17 +2681,34 @@ static int gather_device(const BatchSpec& S, zd_batch* B, DevWalkBufs& WB, std::
   const size_t n = S.n;
   const hipStream_t s = S.stream;
   BatchCarve C;
-  C.carve(n, true, 0, S.with_prefix());
+  C.carve(n, true, 0, S.with_prefix(), S.chain);
   if (int r = batch_arrays(B, C)) return r;
   HIPCHK(hipMemsetAsync(B->d_arr, 0, B->arr_bytes, s));
   lk.lock();
   walk_bufs_on(WB, B->dev);
   if (!WB.h_small && hipHostMalloc((void**)&WB.h_small, 64 * 8, hipHostMallocDefault) != hipSuccess) return ZD_E_HIP;
+  constexpr size_t LCOUNT = 2 * CHAIN_LEVELS + 2;
+  if (S.chain && !WB.h_chain && hipHostMalloc((void**)&WB.h_chain, 4 * LCOUNT, hipHostMallocDefault) != hipSuccess)
+    return ZD_E_HIP;
   const BatchArrays A{B->d_src, B->d_size, B->d_off, B->d_piece0, B->d_out, B->d_cap, B->d_flag, B->d_pfx, B->d_pfx_bytes};
   HIPCHK(launch_batch_layout((const uint64_t*)S.src, S.src_bytes, (const uint64_t*)S.dst, S.dst_cap, (uint32_t)n, A,
                              B->d_scratch, B->d_res, s, (const uint64_t*)S.prefix, S.prefix_bytes));
+  if (S.chain) {
+    // the parents checked, the levels and the chunks grouped by them; the
+    // levels' counts come back with the layout's totals (no wait of their own)
+    HIPCHK(launch_chain_levels(S.parent, (uint32_t)n, B->d_flag, B->d_pfx, B->d_pfx_bytes,
+                               (unsigned long long*)(B->d_res + 3), B->d_par, B->d_lvl, B->d_order, B->d_lcount, s));
+    HIPCHK(hipMemcpyAsync(WB.h_chain, B->d_lcount, 4 * LCOUNT, hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(hipMemcpyAsync(WB.h_small, B->d_res, 4 * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  if (S.chain) {
+    uint32_t levels = 1;
+    for (uint32_t l = 0; l < CHAIN_LEVELS; l++)
+      if (WB.h_chain[l]) levels = l + 1;
+    B->chain_count.assign(WB.h_chain, WB.h_chain + levels);
+    B->chain_links = WB.h_chain[2 * CHAIN_LEVELS];
+  }
   const uint64_t total = WB.h_small[0], npieces = WB.h_small[1];
   if (S.with_prefix()) B->info.prefix_bytes_total = WB.h_small[3];
   B->outbase = (uint8_t*)(uintptr_t)WB.h_small[2];
@@ -2699,6 +2772,16 @@ static int index_host(const BatchSpec& S, zd_batch* B, DevWalkBufs& WB, HostArra
     kept[i] = &hf;
     if (hf.d.kind == ZD_FRAME_ZSTD && hf.key == KEY_NONE) H.bind[i] = chunk_fit(hf, bl, S.dst_cap[i]);
   }
+  // a chain batch: the chained chunks' prefix entries, now that the walk has
+  // the parents' Frame_Content_Sizes and before the planner reads them
+  for (size_t i = 0; S.chain && i < n; i++) {
+    const int64_t p = S.parent[i];
+    if (p < 0) continue;
+    uint64_t z = 0;
+    if (!chain_prefix_bytes(fr[p], &z)) chain_no_prefix_size(fr[i]);
+    P->prefix_bytes[i] = z;
+    P->prefix_ptrs[i] = z ? B->dst[p] : 0;
+  }
   std::vector<HostPart> parts;
   parts_from(kept, bl, parts);
   P->set_parts(std::move(parts));
@@ -2752,6 +2835,9 @@ static int index_device(const BatchSpec& S, zd_batch* B, DevWalkBufs& WB, DevPla
   }
   HIPCHK(launch_batch_fit(d_frames, d_blocks, B->d_cap, B->d_flag, (uint32_t)n, B->d_bind, d_ids, nset,
                           B->dset ? B->dset->fallback : -1, (uint8_t*)in.d_used, s));
+  // a chain batch: the chained chunks' prefix entries, before the planner reads them
+  if (S.chain)
+    HIPCHK(launch_chain_prefix(d_frames, B->d_par, B->d_out, B->outbase, (uint32_t)n, B->d_pfx, B->d_pfx_bytes, s));
   return 0;
 }
 
@@ -2765,7 +2851,9 @@ static int batch_create(const BatchSpec& S, zd_batch** out) {
   if (!out || (S.flags & ZD_F_SKIPPABLE) || n >= (1ull << 31)) return ZD_E_INVALID_ARG;
   if (n && (!S.src || !S.src_bytes || (!S.packed() && (!S.dst || !S.dst_cap)))) return ZD_E_INVALID_ARG;
   if (S.packed() && (!S.on_device || S.dst || S.dst_cap)) return ZD_E_INVALID_ARG;
-  if (S.with_prefix() && (S.dict || S.dset || S.packed() || (n && (!S.prefix || !S.prefix_bytes))))
+  // (a chain batch may come without external prefixes: both arrays null)
+  if (S.with_prefix() && (S.dict || S.dset || S.packed() ||
+                          (n && (S.chain ? !S.prefix != !S.prefix_bytes || !S.parent : !S.prefix || !S.prefix_bytes))))
     return ZD_E_INVALID_ARG;
   if (!S.on_device)
     if (int r = check_entries(S)) return r;
@@ -2780,7 +2868,11 @@ static int batch_create(const BatchSpec& S, zd_batch** out) {
   B->packed = S.packed();
   B->info.nchunks = n;
   B->info.device_built = S.on_device;
+  B->chain = S.chain;
   if (!n) { *out = hold.release(); return ZD_OK; }
+  HostArrays H;
+  if (S.chain && !S.on_device)                // (the last of the argument checks)
+    if (int r = chain_host(S, B, H)) return r;
   HIPCHK(hipGetDevice(&B->dev));
   if ((S.dict && S.dict->dev != B->dev) || (S.dset && S.dset->dev != B->dev)) return ZD_E_INVALID_ARG;
   B->dict = S.dict;
@@ -2790,7 +2882,6 @@ static int batch_create(const BatchSpec& S, zd_batch** out) {
   const auto t0 = std::chrono::steady_clock::now();
 
   // ---- the gathered layout, the chunks' copies ----
-  HostArrays H;
   if (int r = S.on_device ? gather_device(S, B, WB, lk) : gather_host(S, B, H)) return r;
   const auto t1 = std::chrono::steady_clock::now();
 
@@ -2806,12 +2897,19 @@ static int batch_create(const BatchSpec& S, zd_batch** out) {
     P->d_prefix_ptrs = B->d_pfx;
     P->d_prefix_bytes = B->d_pfx_bytes;
   } else if (P->prefix) {
-    P->prefix_ptrs.resize(n);
-    P->prefix_bytes.assign(S.prefix_bytes, S.prefix_bytes + n);
-    for (size_t i = 0; i < n; i++) {
+    P->prefix_ptrs.assign(n, 0);
+    P->prefix_bytes.assign(n, 0);            // (a chained chunk's entry: index_host, from its parent's frame)
+    for (size_t i = 0; S.prefix && i < n; i++) {
+      P->prefix_bytes[i] = S.prefix_bytes[i];
       P->prefix_ptrs[i] = S.prefix_bytes[i] ? (uint64_t)(uintptr_t)S.prefix[i] : 0;
       B->info.prefix_bytes_total += S.prefix_bytes[i];
     }
+  }
+  if (S.chain) {
+    P->chain = true;
+    P->d_chain_order = B->d_order;
+    P->d_chain_parent = B->d_par;
+    P->chain_count = B->chain_count;
   }
   DevPlanIn in;                            // device arrays
   std::unique_ptr<void, Free> set_mem;
@@ -2892,6 +2990,32 @@ int zd_batch_create_device_prefix(const void* const* d_src_ptrs, const uint64_t*
   return batch_create(S, out);
 }
 
+int zd_batch_create_chain(const void* const* d_src, const uint64_t* src_bytes, void* const* d_dst,
+                          const uint64_t* dst_cap, const void* const* d_prefix, const uint64_t* prefix_bytes,
+                          const int64_t* parent, size_t nchunks, uint32_t flags, void* stream, zd_batch** out) {
+  if (nchunks && !parent) return ZD_E_INVALID_ARG;
+  BatchSpec S{d_src, src_bytes, d_dst, dst_cap, d_prefix, prefix_bytes, parent};
+  S.chain = true; S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  return batch_create(S, out);
+}
+
+int zd_batch_create_device_chain(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
+                                 const uint64_t* d_dst_cap, const void* const* d_prefix_ptrs,
+                                 const uint64_t* d_prefix_bytes, const int64_t* d_parent, size_t nchunks,
+                                 uint32_t flags, void* stream, zd_batch** out) {
+  if (nchunks && !d_parent) return ZD_E_INVALID_ARG;
+  BatchSpec S{d_src_ptrs, d_src_bytes, d_dst_ptrs, d_dst_cap, d_prefix_ptrs, d_prefix_bytes, d_parent};
+  S.chain = true; S.on_device = true; S.n = nchunks; S.flags = flags; S.stream = (hipStream_t)stream;
+  return batch_create(S, out);
+}
+
+int zd_batch_chain_info(const zd_batch* B, uint32_t* levels, uint64_t* links) {
+  if (!B || !B->chain) return ZD_E_INVALID_ARG;
+  if (levels) *levels = (uint32_t)std::max<size_t>(B->chain_count.size(), 1);
+  if (links) *links = B->chain_links;
+  return ZD_OK;
+}
+
 int zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
                                  const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict_set* set,
                                  void* stream, zd_batch** out) {
@@ -2969,8 +3093,13 @@ int zd_batch_decode_async(zd_batch* B, void* stream) {
   // every frame at its own destination from the lowest one: never the plan's
   // staging, and no capacity but the frames' own
   if (int r = decode_launch(P, B->d_gather, B->outbase, s)) return r;
-  HIPCHK(launch_batch_results((const FrameState*)(P->d_ws + P->W.frame_state), B->d_bind, (uint32_t)B->n, B->d_status,
-                              B->d_len, s));
+  // (a chain batch: a chunk behind a failed ancestor is ZD_E_NOT_DECODED, known once zd_k_verify has run)
+  if (B->chain)
+    HIPCHK(launch_chain_results((const FrameState*)(P->d_ws + P->W.frame_state), B->d_bind, B->d_par, (uint32_t)B->n,
+                                B->d_status, B->d_len, s));
+  else
+    HIPCHK(launch_batch_results((const FrameState*)(P->d_ws + P->W.frame_state), B->d_bind, (uint32_t)B->n,
+                                B->d_status, B->d_len, s));
   B->launched = true;
   B->have_results = false;
   return ZD_OK;

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "../../include/zd.h"
+#include "zd_chain.h"
 #include "zd_common.h"
 #include "zd_launch.h"
 #include "zd_walk.h"
@@ -3693,6 +3694,47 @@ __global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute_prefix(const uint
                     f_end, gridDim.x, nullptr, M, nullptr, nullptr, nullptr, prefix_ptrs);
 }
 
+// The streaming K4 of a chain batch (zd_batch_create_chain), launched once per
+// level of the chain: workgroup b runs frame order[level_begin + b], the same
+// body as a prefix batch's with prefix_ptrs[f] the parent's destination.  Every
+// frame of the levels below has finished -- the launches of one stream run one
+// after another -- so the parent's state and bytes are final and no workgroup
+// ever waits for another.  A frame whose parent failed, or decoded to another
+// length than the Frame_Content_Size the child was planned with, is
+// ZD_E_NOT_DECODED and reads nothing of the parent's buffer.
+__global__ __launch_bounds__(64, ZD_K4_MINW) void zd_k_execute_chain(const uint8_t* __restrict__ src, uint8_t* outbase,
+                                                   const FrameDesc* __restrict__ frames, FrameState* fstate,
+                                                   const BlockRec* __restrict__ blocks,
+                                                   const CompBlock* __restrict__ comp,
+                                                   const CompState* __restrict__ cstate,
+                                                   const uint8_t* __restrict__ lits,
+                                                   const uint64_t* __restrict__ seqs,
+                                                   const uint16_t* __restrict__ fses,
+                                                   const uint32_t* __restrict__ order, uint32_t level_begin,
+                                                   const int32_t* __restrict__ parent,
+                                                   const uint8_t* const* __restrict__ prefix_ptrs) {
+  __shared__ __attribute__((aligned(16))) uint8_t win[K4_WPAD + K4_C];
+  __shared__ __attribute__((aligned(16))) uint8_t pat[64];
+  __shared__ __attribute__((aligned(16))) uint8_t stab[3 * FSE_TAB];
+  __shared__ __attribute__((aligned(16))) uint8_t stg[K4_STG + 16];
+  __shared__ uint32_t codelut[2 * 64];
+  const K4Lds M{(l_u8*)win + K4_WPAD, (l_u8*)pat, (l_u8*)stab, (l_u8*)stg, (l_u32*)codelut};
+  const uint32_t f = order[level_begin + blockIdx.x];
+  const int32_t p = parent[f];
+  if (p >= 0) {
+    // (wave-uniform: f is the workgroup's; this workgroup alone writes frame f's state in this launch)
+    // a frame the planner gave no block to run (it failed at creation, or holds no zstd frame) keeps its state
+    if (frames[f].nblocks == 0) return;
+    const uint64_t pkey = fstate[p].key, plen = fstate[p].out_len;
+    if (pkey != KEY_NONE || plen != frames[f].out_len0) {
+      if (threadIdx.x == 0) fstate[f].key = make_key(PH_PARSE, 0, PS_STRUCT, 0, ZD_E_NOT_DECODED);
+      return;
+    }
+  }
+  k4_body<false, 2>(src, outbase, frames, fstate, blocks, comp, cstate, lits, seqs, fses, f, f + 1, 1, nullptr, M,
+                    nullptr, nullptr, nullptr, prefix_ptrs);
+}
+
 // ---------------------------------------------------------------------------
 // zd_k_fused: K1's sequence half, K3 and K4 of FZ_FRAMES single-block frames
 // in one workgroup, for plans of few such frames (C3), where K3 is one round
@@ -6081,6 +6123,21 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
   const bool k4_work = a.n_frames > a.n_k4f + a.n_jframes + a.n_k0only;
   auto k4 = [&](uint32_t f0, uint32_t f1, hipStream_t st, const uint8_t* redo) -> hipError_t {
     const uint32_t n = f1 - f0;
+    if (R.k4 == K4_CHAIN) {
+      // one launch per non-empty level, in level order on this stream: a level's
+      // frames find their parents complete.  Levels past the first launch even
+      // when K0 copies every frame whole: the workgroups check their parents.
+      if (n && k4_work) if ((e = dom(DOM_K4, 0)) != hipSuccess) return e;
+      uint32_t begin = 0;
+      for (uint32_t l = 0; l < a.chain_levels; begin += a.chain_count[l], l++)
+        if (a.chain_count[l] && (l || k4_work))
+          hipLaunchKernelGGL(zd_k_execute_chain, dim3(a.chain_count[l]), dim3(64), 0, st, a.src, a.out, frames, fstate,
+                             blocks, comp, (const CompState*)cstate, (const uint8_t*)(ws + W.lits),
+                             (const uint64_t*)seqs, (const uint16_t*)fses, a.chain_order, begin, a.chain_parent,
+                             (const uint8_t* const*)(ws + W.dict_ptrs));
+      if (n && k4_work) if ((e = dom(DOM_K4, 1)) != hipSuccess) return e;
+      return hipSuccess;
+    }
     if (n && k4_work) {  // frames on the streaming K4 (K4F's, K4J's and K0's exit at once)
       const bool tm = !redo && k4_work;
       if (tm) if ((e = dom(DOM_K4, 0)) != hipSuccess) return e;
@@ -6660,6 +6717,143 @@ hipError_t launch_batch_results(const FrameState* fstate, const uint8_t* bind, u
                                 uint64_t* len, hipStream_t s) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(zd_k_batch_results, dim3((n + 255) / 256), dim3(256), 0, s, fstate, bind, n, status, len);
+  return hipGetLastError();
+}
+
+// zd_k_chain_results: the result pass of a chain batch.  Chunk i's own status
+// as zd_k_batch_results gives it; then its ancestors' (the checked parents: no
+// cycle, at most CHAIN_MAX_DEPTH of them), read-only -- one that did not end
+// ZD_OK, zd_k_verify's ZD_E_CHECKSUM_WRONG included, makes the chunk
+// ZD_E_NOT_DECODED with length 0.
+__global__ __launch_bounds__(256) void zd_k_chain_results(const FrameState* __restrict__ fstate,
+                                                          const uint8_t* __restrict__ bind,
+                                                          const int32_t* __restrict__ parent, uint32_t n,
+                                                          int32_t* status, uint64_t* len) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t k = fstate[i].key;
+  int code = key_code(k);
+  if (code == ZD_E_OUT_OF_DOMAIN && key_phase(k) == PH_LIMIT && key_stage(k) == LS_CAPACITY && bind[i])
+    code = ZD_E_DST_TOO_SMALL;
+  int32_t p = parent[i];
+  for (uint32_t hop = 0; p >= 0 && (uint32_t)p < n && hop < CHAIN_MAX_DEPTH; hop++) {
+    if (fstate[p].key != KEY_NONE) { code = ZD_E_NOT_DECODED; break; }
+    p = parent[p];
+  }
+  status[i] = code;
+  len[i] = code ? 0 : fstate[i].out_len;
+}
+
+hipError_t launch_chain_results(const FrameState* fstate, const uint8_t* bind, const int32_t* parent, uint32_t n,
+                                int32_t* status, uint64_t* len, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(zd_k_chain_results, dim3((n + 255) / 256), dim3(256), 0, s, fstate, bind, parent, n, status, len);
+  return hipGetLastError();
+}
+
+// zd_k_chain_levels (zd_batch_create_device_chain): chunk i's parent entry
+// checked and its level found (zd_chain.h chain_level: at most 256 entries of
+// the caller's array read, every index checked before it is used).  A chunk
+// that is refused -- here, or by zd_k_batch_layout before -- has no parent, no
+// prefix and counts as level 0.  The levels' counts through an LDS histogram,
+// one atomic a level and workgroup.
+__global__ __launch_bounds__(256) void zd_k_chain_levels(const int64_t* __restrict__ parent, uint32_t n, uint8_t* flag,
+                                                         uint64_t* pfx, uint64_t* pfx_bytes,
+                                                         unsigned long long* pfx_total, int32_t* par, uint8_t* lvl,
+                                                         uint32_t* lcount) {
+  __shared__ uint32_t hist[CHAIN_LEVELS];
+  __shared__ uint32_t links;
+  hist[threadIdx.x] = 0;
+  if (threadIdx.x == 0) links = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    int32_t L = chain_level(parent, n, i);
+    const int64_t p = parent[i];
+    const uint64_t pz = pfx_bytes[i];
+    const bool bad = flag[i] != CHUNK_OK || L == CHAIN_INVALID || (p >= 0 && pz != 0);
+    if (bad) {
+      if (flag[i] == CHUNK_OK) flag[i] = CHUNK_INVALID;
+      if (pz) {
+        atomicAdd(pfx_total, 0ull - pz);
+        pfx[i] = 0;
+        pfx_bytes[i] = 0;
+      }
+      L = 0;
+    }
+    par[i] = bad ? -1 : (int32_t)p;
+    lvl[i] = (uint8_t)L;
+    atomicAdd(&hist[L], 1u);
+    if (!bad && p >= 0) atomicAdd(&links, 1u);
+  }
+  __syncthreads();
+  if (hist[threadIdx.x]) atomicAdd(&lcount[threadIdx.x], hist[threadIdx.x]);
+  if (threadIdx.x == 0 && links) atomicAdd(&lcount[2 * CHAIN_LEVELS], links);
+}
+// the levels' first places in order[]: lcount[256 + l] = the chunks of the levels below l
+__global__ __launch_bounds__(64) void zd_k_chain_starts(uint32_t* lcount) {
+  if (threadIdx.x != 0) return;
+  uint32_t o = 0;
+  for (uint32_t l = 0; l < CHAIN_LEVELS; l++) { lcount[CHAIN_LEVELS + l] = o; o += lcount[l]; }
+}
+// zd_k_chain_bucket: order[] = the chunks grouped by level (any order inside a
+// level: its frames run concurrently), a workgroup's chunks of one level next
+// to one another through one cursor step per level.
+__global__ __launch_bounds__(256) void zd_k_chain_bucket(const uint8_t* __restrict__ lvl, uint32_t n, uint32_t* order,
+                                                         uint32_t* lcount) {
+  __shared__ uint32_t hist[CHAIN_LEVELS];
+  __shared__ uint32_t base[CHAIN_LEVELS];
+  hist[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  uint32_t L = 0, r = 0;
+  if (i < n) {
+    L = lvl[i];
+    r = atomicAdd(&hist[L], 1u);
+  }
+  __syncthreads();
+  if (hist[threadIdx.x]) base[threadIdx.x] = atomicAdd(&lcount[CHAIN_LEVELS + threadIdx.x], hist[threadIdx.x]);
+  __syncthreads();
+  if (i < n) {
+    const uint32_t at = base[L] + r;
+    if (at < n) order[at] = i;         // (always: the cursors partition [0, n))
+  }
+}
+
+hipError_t launch_chain_levels(const int64_t* parent, uint32_t n, uint8_t* flag, uint64_t* pfx, uint64_t* pfx_bytes,
+                               unsigned long long* pfx_total, int32_t* par, uint8_t* lvl, uint32_t* order,
+                               uint32_t* lcount, hipStream_t s) {
+  if (!n) return hipSuccess;
+  static_assert(CHAIN_LEVELS == 256, "zd_k_chain_levels / _bucket: one histogram slot a thread");
+  const dim3 grid((n + 255) / 256);
+  hipLaunchKernelGGL(zd_k_chain_levels, grid, dim3(256), 0, s, parent, n, flag, pfx, pfx_bytes, pfx_total, par, lvl,
+                     lcount);
+  hipLaunchKernelGGL(zd_k_chain_starts, dim3(1), dim3(64), 0, s, lcount);
+  hipLaunchKernelGGL(zd_k_chain_bucket, grid, dim3(256), 0, s, (const uint8_t*)lvl, n, order, lcount);
+  return hipGetLastError();
+}
+
+// zd_k_chain_prefix: a chained chunk's prefix entry from its parent's indexed
+// frame, one lane per chunk (zd_chain.h chain_prefix_bytes reads the parent's
+// header fields only; the lane writes its own chunk's frame and entries).
+__global__ __launch_bounds__(256) void zd_k_chain_prefix(HostFrame* frames, const int32_t* __restrict__ par,
+                                                         const uint64_t* __restrict__ out, const uint8_t* outbase,
+                                                         uint32_t n, uint64_t* pfx, uint64_t* pfx_bytes) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int32_t p = par[i];
+  if (p < 0 || (uint32_t)p >= n) return;
+  uint64_t z = 0;
+  if (!chain_prefix_bytes(frames[p], &z)) chain_no_prefix_size(frames[i]);
+  pfx_bytes[i] = z;
+  pfx[i] = z ? (uint64_t)(uintptr_t)outbase + out[p] : 0;
+}
+
+hipError_t launch_chain_prefix(HostFrame* frames, const int32_t* par, const uint64_t* out, const uint8_t* outbase,
+                               uint32_t n, uint64_t* pfx, uint64_t* pfx_bytes, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(zd_k_chain_prefix, dim3((n + 255) / 256), dim3(256), 0, s, frames, par, out, outbase, n, pfx,
+                     pfx_bytes);
   return hipGetLastError();
 }
 

@@ -38,6 +38,14 @@ struct LaunchArgs {
   // (Workspace::dict_ptrs, ::frame_dict), a prefix batch (K4_PREFIX) frame f's
   // prefix from dict_ptrs[f]
   const uint8_t* dict = nullptr;
+  // route.k4 == K4_CHAIN (zd_batch_create_chain): the frames grouped by level
+  // (device, n_frames entries), each frame's parent (device, -1: none) and the
+  // levels' frame counts (host, chain_levels entries; level l's frames are
+  // chain_order[sum of the counts below l ...]).  Prefix addresses as K4_PREFIX.
+  const uint32_t* chain_order = nullptr;
+  const int32_t* chain_parent = nullptr;
+  const uint32_t* chain_count = nullptr;
+  uint32_t chain_levels = 0;
 };
 
 // K1 table parse/build -> K2 Huffman literals -> K3 FSE sequences -> K4 execute.
@@ -122,6 +130,32 @@ hipError_t launch_walk_chunks(const uint8_t* gathered, const ChunkList& L, uint3
 // ZD_E_DST_TOO_SMALL).
 hipError_t launch_batch_results(const FrameState* fstate, const uint8_t* bind, uint32_t n, int32_t* status,
                                 uint64_t* len, hipStream_t s);
+// zd_k_chain_results: zd_k_batch_results for a chain batch.  A chunk with an
+// ancestor (parent[], at most 255 hops over the read-only frame states) whose
+// own status is not ZD_OK -- a checksum that zd_k_verify found wrong included
+// -- is ZD_E_NOT_DECODED with length 0.
+hipError_t launch_chain_results(const FrameState* fstate, const uint8_t* bind, const int32_t* parent, uint32_t n,
+                                int32_t* status, uint64_t* len, hipStream_t s);
+
+// A chain batch made from device arrays (zd_batch_create_device_chain), after
+// zd_k_batch_layout.  zd_k_chain_levels, one lane per chunk: the caller's
+// parent entry checked (zd_chain.h chain_level; a bad entry, no root within 255
+// hops, or a prefix size on a chunk with a parent: flag[i] = CHUNK_INVALID, its
+// prefix entry dropped and taken off *pfx_total), par[i] = the checked parent
+// (-1: none or refused), lvl[i] its level, lcount[l] the chunks of level l and
+// lcount[512] the links.  zd_k_chain_bucket: order[] = the chunks by level,
+// through the cursors lcount[256 + l] (one wave scans the counts first).
+// lcount: 2 * 256 + 2 u32, zeroed before.
+hipError_t launch_chain_levels(const int64_t* parent, uint32_t n, uint8_t* flag, uint64_t* pfx, uint64_t* pfx_bytes,
+                               unsigned long long* pfx_total, int32_t* par, uint8_t* lvl, uint32_t* order,
+                               uint32_t* lcount, hipStream_t s);
+// zd_k_chain_prefix, after the capacity pass and before the planner: a chained
+// chunk's prefix entry from its parent's indexed frame (zd_chain.h
+// chain_prefix_bytes) -- the parent's destination, outbase + out[parent], and
+// its Frame_Content_Size; a child whose parent's frame has none is
+// ZD_E_OUT_OF_DOMAIN (its frame's key).
+hipError_t launch_chain_prefix(HostFrame* frames, const int32_t* par, const uint64_t* out, const uint8_t* outbase,
+                               uint32_t n, uint64_t* pfx, uint64_t* pfx_bytes, hipStream_t s);
 
 // A batch made from device arrays (zd_batch_create_device).  The batch's own
 // per-chunk arrays, n entries each; off and piece0 are adjacent (piece0 == off

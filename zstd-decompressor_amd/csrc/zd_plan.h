@@ -438,10 +438,16 @@ struct BatchCarve {
   uint64_t flag = ABSENT;                                 //   u8
   uint64_t scratch = ABSENT, res = ABSENT;                //   u64 words
   uint64_t pfx = ABSENT, pfx_bytes = ABSENT;              //   u64, a prefix batch
+  // a chain batch (zd_batch_create_chain), last of all so that every other
+  // batch's carve is what it was: the checked parent of each chunk (i32, -1:
+  // none), the chunks grouped by level (u32), and with device arrays the
+  // levels' counts and fill cursors (2 * 256 u32), the links (u32, and one of
+  // padding) and each chunk's level (u8)
+  uint64_t par = ABSENT, order = ABSENT, lcount = ABSENT, lvl = ABSENT;
   uint64_t scratch_words = 0;
   uint64_t total = 0;
 
-  void carve(uint64_t n, bool on_device, uint64_t npieces, bool prefixes) {
+  void carve(uint64_t n, bool on_device, uint64_t npieces, bool prefixes, bool chain = false) {
     uint64_t o = 0;
     auto take = [&o](uint64_t bytes) { const uint64_t at = o; o += bytes; return at; };
     src = take(8 * n); size = take(8 * n); off = take(8 * n);
@@ -462,6 +468,11 @@ struct BatchCarve {
       if (prefixes) { pfx = take(8 * n); pfx_bytes = take(8 * n); }
     } else {
       o = bind + plan_align(n, 8);
+    }
+    if (chain) {
+      par = take(4 * n); order = take(4 * n);
+      if (on_device) { lcount = take(4 * (2 * 256 + 2)); lvl = take(n); }
+      o = plan_align(o, 8);
     }
     total = o;
   }

@@ -115,8 +115,9 @@ enum K1Kind : uint8_t {
 // K3: zd_k_sequences (one lane per block) / _q (four lanes) / _l (one block per wave, few-block plans)
 enum K3Kind : uint8_t { K3_ONE_LANE, K3_Q, K3_L };
 // K4: zd_k_execute / _dict (LaunchArgs::dict) / _dicts (each frame's own, from the workspace's table) /
-// _prefix (each frame's own caller-owned prefix, read in place with exact bounds)
-enum K4Kind : uint8_t { K4_PLAIN, K4_DICT, K4_DICT_SET, K4_PREFIX };
+// _prefix (each frame's own caller-owned prefix, read in place with exact bounds) / _chain (a chain batch: the
+// prefix kernel's body, one launch per level of the chain over that level's frames, LaunchArgs::chain_*)
+enum K4Kind : uint8_t { K4_PLAIN, K4_DICT, K4_DICT_SET, K4_PREFIX, K4_CHAIN };
 // Everything launch_pipeline branches on
 struct LaunchRoute {
   bool fused = false;        // K1's sequence half + K3 + K4 as zd_k_fused, then the redo pass

@@ -112,6 +112,12 @@ SIGNATURES = {
                                          C.POINTER(_vp), C.POINTER(C.c_uint64), _sz, C.c_uint32, _vp,
                                          C.POINTER(_vp)]),
     "zd_batch_create_device_prefix": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "zd_batch_create_chain": (C.c_int, [C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(_vp), C.POINTER(C.c_uint64),
+                                        C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), _sz, C.c_uint32,
+                                        _vp, C.POINTER(_vp)]),
+    "zd_batch_create_device_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp,
+                                               C.POINTER(_vp)]),
+    "zd_batch_chain_info": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "zd_chunk_sizes_device": (C.c_int, [_vp, _vp, _sz, C.c_uint32, _vp, _vp, _vp, _vp]),
     "zd_batch_create_device_packed": (C.c_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "zd_batch_create_device_packed_dicts": (C.c_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp,
@@ -254,6 +260,7 @@ REF_PANIC, OUT_OF_DOMAIN, DST_TOO_SMALL, INVALID_ARG, HIP, NO_MEMORY, NOT_DECODE
 DICT_CORRUPTED, DICT_MISMATCH = -98, -99
 CHECKSUM_WRONG = -100  # F_VERIFY_CHECKSUM: the frame decoded, its bytes do not hash to its Content_Checksum
 DICT_SET_MAX = 4096    # ZD_DICT_SET_MAX
+CHAIN_MAX_DEPTH = 255  # ZD_CHAIN_MAX_DEPTH: in-batch ancestors a chunk of a chain batch may have
 F_SKIPPABLE = 1
 F_BLOCK_PARALLEL = 2   # every frame with a compressed block -> K4J (block-parallel execute)
 F_FRAME_SERIAL = 4     # no frame -> K4J

@@ -349,7 +349,11 @@ class Batch:
     ptrs[i] -- its own raw-content prefix, as ZSTD_DCtx_refPrefix gives a frame;
     size 0, address None or 0: no prefix.  Prefixes are read by decode_async
     where they lie, must stay valid while the batch lives and must not overlap
-    a destination; not together with dictionary=).
+    a destination; not together with dictionary=; parents: a delta chain,
+    zd_batch_create_chain -- parents[i] is -1, or the index of the chunk whose
+    decoded output OF THE SAME LAUNCH is chunk i's prefix (its prefix size must
+    then be 0; prefixes may be None when no chunk has an external one).  A chunk
+    behind a failed ancestor is NOT_DECODED; `chain_info` gives the levels).
 
     src_ptrs / dst_ptrs are device addresses (integers, e.g. tensor.data_ptr()),
     src_sizes / dst_caps byte counts.  A chunk holds one zstd frame (skippable
@@ -358,20 +362,32 @@ class Batch:
     stay valid while the batch decodes."""
 
     def __init__(self, src_ptrs, src_sizes, dst_ptrs, dst_caps, flags: int = 0, dictionary=None, stream: int = 0,
-                 prefixes=None):
+                 prefixes=None, parents=None):
         n = len(src_ptrs)
         if not (len(src_sizes) == len(dst_ptrs) == len(dst_caps) == n):
             raise ValueError("src_ptrs, src_sizes, dst_ptrs and dst_caps differ in length")
         name, dh = _with_dictionary("zd_batch_create", dictionary)
-        if prefixes is not None and dictionary is not None:
-            raise ValueError("prefixes= and dictionary= exclude one another")
+        if (prefixes is not None or parents is not None) and dictionary is not None:
+            raise ValueError("prefixes= / parents= and dictionary= exclude one another")
         sp, ss, dp, dc = (_u64_array(v, n) for v in (src_ptrs, src_sizes, dst_ptrs, dst_caps))
         vpp = C.POINTER(C.c_void_p)
+        pp = ps = None
         if prefixes is not None:
             pptrs, psizes = prefixes
             if not (len(pptrs) == len(psizes) == n):
                 raise ValueError("the prefixes and the chunks differ in length")
             pp, ps = _u64_array(pptrs, n), _u64_array(psizes, n)
+        if parents is not None:
+            # a chain batch (zd_batch_create_chain): parents[i] = -1, or the chunk whose output of the
+            # same launch is chunk i's prefix
+            if len(parents) != n:
+                raise ValueError("the parents and the chunks differ in length")
+            import array
+            pa = array.array("q", [int(v) for v in parents])
+            par = (C.c_int64 * n).from_buffer(pa) if n else (C.c_int64 * 1)()
+            self._create("zd_batch_create_chain", n, C.cast(sp, vpp), ss, C.cast(dp, vpp), dc,
+                         C.cast(pp, vpp) if pp is not None else None, ps, par, n, flags, C.c_void_p(stream))
+        elif prefixes is not None:
             self._create("zd_batch_create_prefix", n, C.cast(sp, vpp), ss, C.cast(dp, vpp), dc, C.cast(pp, vpp), ps,
                          n, flags, C.c_void_p(stream))
         else:
@@ -388,7 +404,7 @@ class Batch:
 
     @classmethod
     def from_device(cls, src_ptrs, src_sizes, dst_ptrs, dst_caps, nchunks=None, flags: int = 0, dictionary=None,
-                    stream: int = 0, prefixes=None):
+                    stream: int = 0, prefixes=None, parents=None):
         """zd_batch_create_device: the same batch from a chunk table that is on
         the device.  Each of the four arrays is a contiguous int64 / uint64
         device tensor of one entry a chunk, or the device address of such an
@@ -401,17 +417,27 @@ class Batch:
         prefixes: a pair (ptrs, sizes) of two more such arrays, chunk i's own
         prefix (zd_batch_create_device_prefix; not together with dictionary=);
         a NULL prefix address with a non-zero size fails its own chunk, and
-        keeping prefixes and destinations apart is the caller's duty."""
-        if prefixes is not None and dictionary is not None:
-            raise ValueError("prefixes= and dictionary= exclude one another")
+        keeping prefixes and destinations apart is the caller's duty.
+        parents: one more such array, int64 (zd_batch_create_device_chain; with
+        or without prefixes=): chunk i's parent in the batch, or -1.  A bad
+        entry, a cycle or a chain deeper than 255 fails its own chunks with
+        INVALID_ARG."""
+        if (prefixes is not None or parents is not None) and dictionary is not None:
+            raise ValueError("prefixes= / parents= and dictionary= exclude one another")
         arrs = (src_ptrs, src_sizes, dst_ptrs, dst_caps) + (tuple(prefixes) if prefixes is not None else ())
         if len(arrs) not in (4, 6):
             raise ValueError("prefixes is a pair (ptrs, sizes)")
+        if parents is not None:
+            arrs = arrs + (parents,)
         n, addr, keep = _device_arrays(arrs, nchunks, lists=False)
         name, dh = _with_dictionary("zd_batch_create_device", dictionary)
         self = cls.__new__(cls)
         ptrs = [C.c_void_p(a) for a in addr]
-        if prefixes is not None:
+        if parents is not None:
+            if prefixes is None:
+                ptrs[4:4] = [None, None]
+            self._create("zd_batch_create_device_chain", n, *ptrs, n, flags, C.c_void_p(stream))
+        elif prefixes is not None:
             self._create("zd_batch_create_device_prefix", n, *ptrs, n, flags, C.c_void_p(stream))
         else:
             self._create(name, n, *ptrs, n, flags, dh, C.c_void_p(stream))
@@ -437,6 +463,15 @@ class Batch:
         _lib.check(_lib.lib().zd_batch_output_layout(self._h, C.byref(ob), None, None), "zd_batch_output_layout")
         self.out_bytes = ob.value
         return self
+
+    @property
+    def chain_info(self):
+        """zd_batch_chain_info: (levels, links) of a batch made with parents= --
+        the chain's levels (1 when no chunk has a parent) and the chunks with a
+        parent.  ZdError(INVALID_ARG) on any other batch."""
+        lv, ln = C.c_uint32(), C.c_uint64()
+        _lib.check(_lib.lib().zd_batch_chain_info(self._h, C.byref(lv), C.byref(ln)), "zd_batch_chain_info")
+        return lv.value, ln.value
 
     def output_layout(self):
         """A packed batch's (device address of the uint64 offsets, device address
@@ -517,10 +552,12 @@ class Batch:
             pass
 
 
-def decode_tensors(srcs, dsts, dictionary=None, flags: int = 0, prefixes=None):
+def decode_tensors(srcs, dsts, dictionary=None, flags: int = 0, prefixes=None, parents=None):
     """Decode uint8 device tensors srcs[i] (one chunk each) into dsts[i] on
     torch's current stream: (statuses, lengths).  prefixes: one entry a chunk,
-    a uint8 device tensor (the chunk's own prefix, read in place) or None."""
+    a uint8 device tensor (the chunk's own prefix, read in place) or None.
+    parents: one entry a chunk, -1 or the index of the chunk whose output of
+    this decode is the chunk's prefix (a delta chain; Batch parents=)."""
     import torch
     if len(srcs) != len(dsts):
         raise ValueError("srcs and dsts differ in length")
@@ -536,7 +573,7 @@ def decode_tensors(srcs, dsts, dictionary=None, flags: int = 0, prefixes=None):
                [p.numel() if p is not None else 0 for p in prefixes])
     b = Batch([t.data_ptr() if t.numel() else 0 for t in srcs], [t.numel() for t in srcs],
               [t.data_ptr() if t.numel() else 0 for t in dsts], [t.numel() for t in dsts],
-              flags=flags, dictionary=dictionary, stream=stream, prefixes=pfx)
+              flags=flags, dictionary=dictionary, stream=stream, prefixes=pfx, parents=parents)
     try:
         b.decode_async(stream)
         return b.results(stream)
