@@ -152,8 +152,14 @@ typedef struct zd_plan zd_plan;
 
 #define ZD_F_SKIPPABLE  1u  /* append skippable-frame payloads to the output (CLI -p, src/main.rs:45-48) */
 /* Executor choice for frames of many blocks; default:
- * automatic.  Same output either way; tests run both. */
-#define ZD_F_BLOCK_PARALLEL 2u  /* every frame with a compressed block -> K4J (block-parallel execute) */
+ * automatic.  Same output either way; tests run both.  Plans with a
+ * dictionary or a dictionary set, chain batches and zd_context ignore both
+ * flags (the streaming executor only); a prefix batch (zd_batch_create_prefix,
+ * zd_batch_create_device_prefix) ignores the automatic rule and takes K4J only
+ * when ZD_F_BLOCK_PARALLEL asks for it: large deltas, whose hundreds of blocks
+ * one wave would decode one after another. */
+#define ZD_F_BLOCK_PARALLEL 2u  /* every frame with a compressed block -> K4J (block-parallel execute);
+                                   prefix batches included */
 #define ZD_F_FRAME_SERIAL   4u  /* no frame -> K4J (the streaming per-frame executor) */
 /* Sequence-decode choice: K3 with one lane per block instead of four (the
  * default, K3Q).  Same records either way; tests run both. */
@@ -211,6 +217,16 @@ typedef struct zd_plan zd_plan;
  * decoded.  zd_context / zd_block_decode / zd_execute_sequences take no flags
  * and stay outside the feature. */
 #define ZD_F_VERIFY_CHECKSUM 1024u
+/* Accept frames whose Window_Size is up to 2 GiB (1 << 31) where the default
+ * keeps the reference's 8 MiB limit (frame.rs:44): what `zstd --long` and
+ * `zstd --patch-from` write for inputs past 8 MiB.  Above 2 GiB a frame is
+ * still ZD_E_WINDOW_SIZE_TOO_BIG.  A plan / batch flag, accepted wherever plan
+ * flags are (the host walk, the device walks, zd_plan_decompress's re-plans,
+ * the streaming re-decode inside zd_batch_results); zd_chunk_sizes_device has
+ * ZD_SIZES_LONG_WINDOW.  Routing is untouched: no executor depends on the
+ * window, each checks an offset against the bytes produced so far.  Without
+ * the flag nothing changes.  zd_context keeps its own window check. */
+#define ZD_F_LONG_WINDOW 2048u
 
 /* zd_plan_info.executors: */
 #define ZD_EXEC_FUSED 1u   /* zd_k_fused: tables, FSE chains and execution per group of four
@@ -617,13 +633,22 @@ int  zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t*
  *    zstd frame per chunk with skippable frames skipped, a status of its own for
  *    every chunk, length 0 on failure, nothing written outside [d_dst[i],
  *    d_dst[i] + dst_cap[i]).
- *  - Executors.  The streaming executor only, like dictionary batches:
- *    zd_batch_info.executors is 0 and ZD_F_BLOCK_PARALLEL is ignored.  A chunk
- *    whose prefix size plus capacity passes the executor's int32 positions
+ *  - Executors.  Without ZD_F_BLOCK_PARALLEL the streaming executor only,
+ *    like dictionary batches: zd_batch_info.executors is 0.  A chunk whose
+ *    prefix size plus capacity passes that executor's int32 positions
  *    (0x7FFF0000) is ZD_E_OUT_OF_DOMAIN, alone, whether or not its frame has
- *    sequences.  Frames keep the reference's 8 MiB window limit, so a
- *    --patch-from archive made with --long beyond 8 MiB is refused, as in any
- *    plan here.
+ *    sequences.  With ZD_F_BLOCK_PARALLEL every frame of the batch with a
+ *    compressed block executes block-parallel (K4J; executors carries
+ *    ZD_EXEC_K4J), the others on the streaming executor as before.  For a K4J
+ *    frame the prefix alone must fit 0x7FFF0000 bytes and the capacity K4J's
+ *    32 GiB: a 1.5 GiB shard decodes against its 1.5 GiB predecessor.  A chunk
+ *    whose block-parallel execution did not converge is decoded again on the
+ *    streaming executor inside zd_batch_results, with its prefix; there a
+ *    prefix plus capacity past 0x7FFF0000 ends ZD_E_OUT_OF_DOMAIN.  The same
+ *    bytes and statuses either way.
+ *  - Window.  Frames keep the reference's 8 MiB window limit unless the batch
+ *    has ZD_F_LONG_WINDOW (up to 2 GiB): a --patch-from archive of a file
+ *    past 8 MiB needs it.
  *  - Read bounds.  No byte outside [d_prefix[i], d_prefix[i] + prefix_bytes[i])
  *    is ever read through a prefix pointer, at any alignment: the caller owes
  *    no padding on either side.
@@ -643,8 +668,10 @@ int  zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t*
  * prefix_bytes[i] > 0; a prefix range that wraps; a prefix range that overlaps
  * a destination range.  nchunks == 0 is ZD_OK.
  * Limits (not in this interface): no packed prefix batches; prefixes cannot be
- * re-pointed after creation; no prefixes on the LDS-resident, block-parallel or
- * fused executors; none in zd_plan_*, the sharded calls or zd_context.  (A
+ * re-pointed after creation; no prefixes on the LDS-resident or fused
+ * executors, and on the block-parallel one only by ZD_F_BLOCK_PARALLEL (no
+ * automatic rule yet); none in zd_plan_*, the sharded calls or zd_context;
+ * no window past 2 GiB.  (A
  * chunk whose prefix is another chunk's output of the same launch: a chain
  * batch, zd_batch_create_chain.) */
 int  zd_batch_create_prefix(const void* const* d_src, const uint64_t* src_bytes,
@@ -770,11 +797,14 @@ int  zd_batch_chain_info(const zd_batch* batch, uint32_t* levels, uint64_t* link
  * when it is decoded.
  * flags: ZD_SIZES_DICT when the chunks will be decoded with a dictionary or a
  * set (an empty Raw literals section is then accepted, as in a dictionary
- * plan; without it such a chunk is ZD_E_EMPTY_SLICE).
+ * plan; without it such a chunk is ZD_E_EMPTY_SLICE), a prefix batch included;
+ * ZD_SIZES_LONG_WINDOW when they will be decoded with ZD_F_LONG_WINDOW (a
+ * Window_Size up to 2 GiB is then no failure; the bit is that flag's own).
  * ZD_E_INVALID_ARG, before any HIP call: a NULL d_src_ptrs, d_src_bytes or
  * d_size with nchunks > 0, nchunks >= 2^31, unknown flag bits.  nchunks == 0 is
  * ZD_OK without a HIP call. */
 #define ZD_SIZES_DICT 1u
+#define ZD_SIZES_LONG_WINDOW 2048u   /* the chunks will be decoded with ZD_F_LONG_WINDOW (the same bit) */
 int  zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
                            uint32_t flags, uint64_t* d_size, int32_t* d_status, uint8_t* d_exact, void* stream);
 /* zd_batch_create_device without destinations: a PACKED batch lays its outputs

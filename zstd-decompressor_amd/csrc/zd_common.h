@@ -18,6 +18,13 @@ constexpr int FSE_MAX_AL = 9;                    // MAX_AL (fse.rs:13)
 constexpr int FSE_ENTRIES = 1 << FSE_MAX_AL;     // u32 entries per table
 constexpr int MAX_WEIGHTS = 2048;                // cap on FSE-decoded Huffman weights
 constexpr uint64_t MAX_WIN_SIZE = 8ull << 20;    // frame.rs:44
+constexpr uint64_t MAX_WIN_SIZE_LONG = 1ull << 31;   // with ZD_F_LONG_WINDOW (no executor depends on the window)
+// The walk's options (zd_walk.h index_frame / index_chunk): parse_compressed's
+// rfc_empty_lits (dictionary, set and prefix plans), ZD_F_LONG_WINDOW's limit
+constexpr uint32_t WALK_RFC_EMPTY_LITS = 1u, WALK_LONG_WINDOW = 2u;
+ZD_HD inline uint32_t walk_opts(bool rfc_empty_lits, bool long_window) {
+  return (rfc_empty_lits ? WALK_RFC_EMPTY_LITS : 0u) | (long_window ? WALK_LONG_WINDOW : 0u);
+}
 constexpr uint32_t MAX_BLOCK_OUT = 128u << 10;   // RFC Block_Maximum_Size (capacity bound only)
 
 // LUT entry: symbol | nbits << 8 | ABSENT (depth of the absent tree node in nbits)

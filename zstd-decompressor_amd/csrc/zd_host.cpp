@@ -155,6 +155,8 @@ struct zd_plan {
   const int32_t* d_chain_parent = nullptr;
   std::vector<uint32_t> chain_count;
   bool with_dict() const { return dict != nullptr || dset != nullptr || prefix; }
+  // the walk's options (zd_walk.h): parse_compressed's rfc_empty_lits, ZD_F_LONG_WINDOW
+  uint32_t walk_opts() const { return zd::walk_opts(with_dict(), (flags & ZD_F_LONG_WINDOW) != 0); }
   std::vector<HostPart> parts;          // the host walk's frames, in input order
   std::vector<size_t> part_f0;          // plan frame index of each part's first frame
   size_t nframes = 0;
@@ -418,7 +420,10 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   X.k4j_mode = k4j_mode_of(P->flags, route_env());
   X.k4j_min = P->nframes <= K4J_FEW_FRAMES ? K4J_MIN_BLOCKS_FEW : K4J_MIN_BLOCKS;
   X.k4j_auto = X.k4j_mode < 0 && out_len0 == 0 && j_candidates > 0 && j_candidates <= K4J_MAX_FRAMES;
-  if (X.dict) { X.k4j_auto = false; X.k4j_mode = 0; }
+  if (X.dict) {
+    X.k4j_auto = false;
+    X.k4j_mode = k4j_mode_behind(X.k4j_mode, P->flags, true, P->prefix, P->chain);
+  }
   return X;
 }
 
@@ -939,11 +944,11 @@ void aux_give(zd_plan* P) {
 // Frames from in (FrameIterator::next, frame.rs:94-99) into `part` until the
 // input ends, a frame starting at or past `stop` comes up, or one fails (kept,
 // with its status).
-int index_frames(const uint8_t* src, Bytes& in, size_t stop, HostPart& part, bool rfc_empty_lits) {
+int index_frames(const uint8_t* src, Bytes& in, size_t stop, HostPart& part, uint32_t wopt) {
   while (in.n && (size_t)(in.p - src) < stop) {
     HostFrame hf;
     VecSink sink{part.blocks};
-    int r = index_frame(src, in, &hf, sink, rfc_empty_lits);
+    int r = index_frame(src, in, &hf, sink, wopt);
     part.frames.push_back(hf);
     if (r) return r;
   }
@@ -982,7 +987,7 @@ int plan_index(zd_plan* P, const uint8_t* src, size_t n) {
   static const char* wt = getenv("ZD_WALK_THREADS");   // experiments
   const unsigned hw = wt ? (unsigned)std::max(1, atoi(wt)) : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   const size_t T = n >= PAR_INDEX_MIN_BYTES ? std::min<size_t>(hw, n >> 20) : 1;
-  const bool rfc_empty_lits = P->with_dict();   // (zd_walk.h parse_compressed)
+  const uint32_t wopt = P->walk_opts();          // (zd_walk.h parse_compressed, the window limit)
   std::vector<HostPart> part(T);
   std::vector<int> st(T, 0);
   std::vector<size_t> end(T, 0), cut(T + 1);
@@ -1003,7 +1008,7 @@ int plan_index(zd_plan* P, const uint8_t* src, size_t n) {
       }
       part[k].blocks.reserve((cut[k + 1] - cut[k]) / (16u << 10) + 16);
       Bytes in{src + p, n - p};
-      st[k] = index_frames(src, in, cut[k + 1], part[k], rfc_empty_lits);
+      st[k] = index_frames(src, in, cut[k + 1], part[k], wopt);
       end[k] = (size_t)(in.p - src);
       // a candidate that fails at once was a magic inside data: look further
       if (k && st[k] && part[k].frames.size() == 1) {
@@ -1044,7 +1049,7 @@ int plan_index(zd_plan* P, const uint8_t* src, size_t n) {
     while (in.n) {
       HostFrame hf;
       VecSink sink{tail.blocks};
-      const int r = index_frame(src, in, &hf, sink, rfc_empty_lits);
+      const int r = index_frame(src, in, &hf, sink, wopt);
       tail.frames.push_back(hf);
       const size_t p = (size_t)(in.p - src);
       serial += p - cur;
@@ -1234,9 +1239,9 @@ int dev_walk_download(DevWalkBufs& B, hipStream_t s, const HostFrame** frames, c
 // summaries with f_off / b_off, frames / blocks (pinned) the fill pass.
 int dev_walk(DevWalkBufs& B, const uint8_t* d_src, uint64_t n, uint64_t first, uint64_t chunk, uint32_t nranges,
              hipStream_t s, uint64_t* F_out, uint64_t* B_out, const HostFrame** frames, const HostBlock** blocks,
-             bool download = true) {
+             bool download = true, uint32_t wopt = 0) {
   if (!grow_dev(B.d_wr, B.cap_wr, nranges) || !grow_pinned(B.h_wr, B.cap_hwr, nranges)) return ZD_E_HIP;
-  if (launch_walk(d_src, n, first, chunk, nranges, B.d_wr, nullptr, nullptr, false, s) != hipSuccess ||
+  if (launch_walk(d_src, n, first, chunk, nranges, B.d_wr, nullptr, nullptr, false, s, wopt) != hipSuccess ||
       hipMemcpyAsync(B.h_wr, B.d_wr, nranges * sizeof(WalkRange), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return ZD_E_HIP;
@@ -1253,7 +1258,7 @@ int dev_walk(DevWalkBufs& B, const uint8_t* d_src, uint64_t n, uint64_t first, u
   HostFrame* d_frames = (HostFrame*)B.d_out;
   HostBlock* d_blocks = (HostBlock*)(B.d_out + fb);
   if (hipMemcpyAsync(B.d_wr, B.h_wr, nranges * sizeof(WalkRange), hipMemcpyHostToDevice, s) != hipSuccess ||
-      launch_walk(d_src, n, first, chunk, nranges, B.d_wr, d_frames, d_blocks, true, s) != hipSuccess)
+      launch_walk(d_src, n, first, chunk, nranges, B.d_wr, d_frames, d_blocks, true, s, wopt) != hipSuccess)
     return ZD_E_HIP;
   B.fb = fb;
   B.bytes = bytes;
@@ -1437,7 +1442,7 @@ int plan_index_dev(zd_plan* P, const uint8_t* d_src, size_t n, hipStream_t s) {
     uint64_t F = 0, NB = 0;
     const HostFrame* fr = nullptr;
     const HostBlock* bl = nullptr;
-    if (int r = dev_walk(B, d_src, n, 0, chunk, T, s, &F, &NB, &fr, &bl, false)) return r;
+    if (int r = dev_walk(B, d_src, n, 0, chunk, T, s, &F, &NB, &fr, &bl, false, P->walk_opts())) return r;
     t_walk = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
     const auto cut = [&](size_t k) { return std::min<uint64_t>((uint64_t)k * chunk, n); };
     // The common case from the range summaries alone: every range's chain
@@ -1519,7 +1524,7 @@ int plan_index_dev(zd_plan* P, const uint8_t* d_src, size_t n, hipStream_t s) {
         const HostFrame* fr2 = nullptr;
         const HostBlock* bl2 = nullptr;
         const uint64_t hi = std::max<uint64_t>(cut(kk + 1), cur + 1);
-        if (int r = dev_walk(B, d_src, n, cur, hi - cur, 1, s, &F2, &NB2, &fr2, &bl2)) return r;
+        if (int r = dev_walk(B, d_src, n, cur, hi - cur, 1, s, &F2, &NB2, &fr2, &bl2, true, P->walk_opts())) return r;
         std::vector<const HostFrame*> t2;
         for (uint64_t i = 0; i < F2; i++) t2.push_back(fr2 + i);
         parts_from(t2, bl2, keep);
@@ -2722,7 +2727,7 @@ static int gather_device(const BatchSpec& S, zd_batch* B, DevWalkBufs& WB, std::
 
 // zd_k_walk_chunks' count pass: d_nblk[i] = the blocks chunk i's walk keeps
 static int walk_count(zd_batch* B, hipStream_t s) {
-  HIPCHK(launch_walk_chunks(B->d_gather, ChunkList{B->d_src, B->d_size, B->d_off}, (uint32_t)B->n, B->P->with_dict(),
+  HIPCHK(launch_walk_chunks(B->d_gather, ChunkList{B->d_src, B->d_size, B->d_off}, (uint32_t)B->n, B->P->walk_opts(),
                             B->d_nblk, nullptr, nullptr, nullptr, false, s));
   return 0;
 }
@@ -2737,7 +2742,7 @@ static int walk_fill(zd_batch* B, DevWalkBufs& WB, uint64_t NB, const uint64_t* 
   WB.fb = fb;
   WB.bytes = bytes;
   if (h_boff) HIPCHK(hipMemcpyAsync(B->d_boff, h_boff, 8 * n, hipMemcpyHostToDevice, s));
-  HIPCHK(launch_walk_chunks(B->d_gather, ChunkList{B->d_src, B->d_size, B->d_off}, (uint32_t)n, B->P->with_dict(),
+  HIPCHK(launch_walk_chunks(B->d_gather, ChunkList{B->d_src, B->d_size, B->d_off}, (uint32_t)n, B->P->walk_opts(),
                             B->d_nblk, B->d_boff, (HostFrame*)WB.d_out, (HostBlock*)(WB.d_out + fb), true, s));
   return 0;
 }
@@ -3064,11 +3069,11 @@ int zd_batch_bind_output(zd_batch* B, void* d_out, uint64_t cap) {
 
 int zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks, uint32_t flags,
                           uint64_t* d_size, int32_t* d_status, uint8_t* d_exact, void* stream) {
-  if ((flags & ~ZD_SIZES_DICT) || nchunks >= (1ull << 31)) return ZD_E_INVALID_ARG;
+  if ((flags & ~(ZD_SIZES_DICT | ZD_SIZES_LONG_WINDOW)) || nchunks >= (1ull << 31)) return ZD_E_INVALID_ARG;
   if (nchunks && (!d_src_ptrs || !d_src_bytes || !d_size)) return ZD_E_INVALID_ARG;
   if (!nchunks) return ZD_OK;
-  HIPCHK(launch_chunk_sizes((const uint64_t*)d_src_ptrs, d_src_bytes, (uint32_t)nchunks, (flags & ZD_SIZES_DICT) != 0,
-                            d_size, d_status, d_exact, (hipStream_t)stream));
+  HIPCHK(launch_chunk_sizes((const uint64_t*)d_src_ptrs, d_src_bytes, (uint32_t)nchunks,
+                            walk_opts((flags & ZD_SIZES_DICT) != 0, (flags & ZD_SIZES_LONG_WINDOW) != 0), d_size, d_status, d_exact, (hipStream_t)stream));
   return ZD_OK;
 }
 
@@ -3158,9 +3163,28 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
         dst[k] = (void*)(uintptr_t)B->dst[i];
         dc[k] = B->dst_cap[i];
       }
-      // (no prefixes to hand on: plan_ctx turns K4J off for every dictionary,
-      // set and prefix plan, so such a batch never has n_jframes)
+      // a prefix batch (K4J only with ZD_F_BLOCK_PARALLEL): the redo chunks'
+      // checked prefix addresses and sizes go with them -- a chunk whose prefix
+      // plus capacity the streaming executor cannot hold ends ZD_E_OUT_OF_DOMAIN.
+      // (plan_ctx turns K4J off for every dictionary, set and chain plan, so
+      // such a batch never has n_jframes)
+      std::vector<const void*> pf;
+      std::vector<uint64_t> pz;
+      if (P->prefix) {
+        std::vector<uint64_t> a = P->prefix_ptrs, z = P->prefix_bytes;
+        if (P->d_prefix_ptrs) {
+          a.resize(n); z.resize(n);
+          HIPCHK(hipMemcpy(a.data(), P->d_prefix_ptrs, 8 * n, hipMemcpyDeviceToHost));
+          HIPCHK(hipMemcpy(z.data(), P->d_prefix_bytes, 8 * n, hipMemcpyDeviceToHost));
+        }
+        pf.resize(m); pz.resize(m);
+        for (size_t k = 0; k < m; k++) {
+          pz[k] = z[redo[k]];
+          pf[k] = pz[k] ? (const void*)(uintptr_t)a[redo[k]] : nullptr;
+        }
+      }
       BatchSpec S{src.data(), sz.data(), dst.data(), dc.data()};
+      if (P->prefix) { S.prefix = pf.data(); S.prefix_bytes = pz.data(); }
       S.n = m;
       S.flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_J_ONE_ROUND)) | ZD_F_FRAME_SERIAL;
       S.dict = B->dict;

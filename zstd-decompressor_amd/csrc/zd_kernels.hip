@@ -4935,7 +4935,9 @@ __global__ __launch_bounds__(K4F_T) void zd_k_execute_lds(const uint8_t* __restr
 //                     state word is J_FINAL | byte, every match byte's the
 //                     distance to the byte it copies (off, plus off per period
 //                     passed in an overlapping match: the reference's
-//                     byte-by-byte push)
+//                     byte-by-byte push); in a prefix batch (zd_k_jscatter<true>) a match
+//                     byte whose source lies in the frame's prefix is final
+//                     here too, J_FINAL | that prefix byte
 //   KJ4 zd_k_jround   pointer jumping, in place: S[p] = S[p - S[p]] for every
 //                     pending word, up to j_hops (6) hops per word and round (a final
 //                     source hands over its byte, a pending one adds its
@@ -5395,6 +5397,25 @@ __device__ void j_fill_lits(uint32_t* st, uint64_t P0, uint32_t n, const uint8_t
 #define ZD_JS_STAGE 1
 #endif
 constexpr uint32_t JS_STG = 2048;
+// The state word of a match byte at frame position y that copies the byte d
+// back.  PFX (a prefix batch, zd_k_jscatter<true>): a source before the
+// frame's first byte is prefix byte P - (d - y) -- the checks keep d - y <= P,
+// so the read stays inside [pfx, pfx + P) and never happens when P = 0 -- and
+// final before the launch starts: the word is J_FINAL | that byte, and every
+// distance the rounds follow points inside the frame.
+template <bool PFX>
+__device__ __attribute__((always_inline)) inline uint32_t j_match_word(uint32_t d, uint64_t y,
+                                                                       const uint8_t* __restrict__ pfx, uint32_t P) {
+  if constexpr (PFX)
+    if (d > y) return J_FINAL | (uint32_t)pfx[P - (uint32_t)(d - y)];
+  return d;
+}
+// PFX (a prefix batch's K4J frames, ZD_F_BLOCK_PARALLEL): frame f decodes
+// behind its own prefix, pfx_ptrs[f] of frames[f].out_len0 bytes
+// (Workspace::dict_ptrs, as zd_k_execute_prefix reads it; both wave-uniform).
+// Without it the two arguments are never read and the kernel's instructions
+// are what they were before prefix batches came to K4J.
+template <bool PFX>
 __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ src, FrameState* fstate,
                                                     const BlockRec* __restrict__ blocks,
                                                     const CompBlock* __restrict__ comp,
@@ -5404,7 +5425,8 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
                                                     const JFrame* __restrict__ jframes,
                                                     const JBlkDesc* __restrict__ jd, const JBlk* __restrict__ jb,
                                                     const JSeg* __restrict__ jseg, const JSegDesc* __restrict__ jsd,
-                                                    uint32_t* jst) {
+                                                    uint32_t* jst, const FrameDesc* __restrict__ frames,
+                                                    const uint8_t* const* __restrict__ pfx_ptrs) {
   __shared__ __attribute__((aligned(16))) uint8_t stab[3][FSE_TAB];
   __shared__ uint32_t sa[65], sll[64], soff[64], slp[64];
 #if ZD_JS_STAGE
@@ -5423,6 +5445,13 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
   if (B.type != 2) {
     j_fill_lits(st, pos, B.size, B.type == 1 ? nullptr : src + B.src, B.rle, lane);
     return;
+  }
+  // the frame's prefix (the planner keeps its size below K4_MAX_FRAME_OUT)
+  const uint8_t* pfx = nullptr;
+  uint32_t P = 0;
+  if constexpr (PFX) {
+    pfx = pfx_ptrs[JF.frame];
+    P = (uint32_t)frames[JF.frame].out_len0;
   }
   const CompBlock C = comp[B.comp];
   const CompState CS = cstate[B.comp];
@@ -5456,7 +5485,8 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
       // checks (decoding_context.rs:84-90, D9), in sequence order
       const uint64_t before = (uint64_t)pos + opos;
       const bool dbad = valid && lane == bl;
-      const bool imp = valid && !dbad && ((uint64_t)lit_cursor + lpos + ll > nl || off > before + ll);
+      // (a prefix frame: the P prefix bytes lie before the frame's first)
+      const bool imp = valid && !dbad && ((uint64_t)lit_cursor + lpos + ll > nl || off > before + ll + P);
       const bool panic = valid && !dbad && !imp && ml != 0 && off == 0;
       // a match byte's state word is its distance to the byte it copies
       // (< J_FINAL): only a frame past 2 GiB reaches further (the streaming
@@ -5514,6 +5544,20 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
           r = jj < o ? jj : jj % o;
         }
         uint32_t w[16];
+        if constexpr (PFX) {
+          // a whole piece inside one match and one period of it, whose sixteen
+          // sources are sixteen consecutive prefix bytes (the last one still
+          // before the frame's first byte): one 16-byte load, any alignment
+          const uint32_t d0 = o + jj - r;
+          const uint64_t y0 = pos + x0;
+          if (inm && x1 - x0 == 16 && x0 + 16 <= nx && r + 16 <= o && d0 >= y0 + 16) {
+            const u32x4 v = ldg16(pfx + (P - (uint32_t)(d0 - y0)));
+#pragma unroll
+            for (uint32_t b = 0; b < 16; b++) w[b] = J_FINAL | ((v[b >> 2] >> (8 * (b & 3))) & 255);
+            j_store_words(st + pos + x0, w, 16);
+            continue;
+          }
+        }
 #pragma unroll
         for (uint32_t b = 0; b < 16; b++) {
           const uint32_t x = x0 + b;
@@ -5533,7 +5577,8 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
               }
             }
             const uint32_t q = lp + (x - a) - lit_cursor;   // the byte's literal, relative to the stage
-            w[b] = inm ? o + jj - r : J_FINAL | (staged ? (uint32_t)slit[q] : lsrc ? (uint32_t)lsrc[lp + (x - a)] : lfill);
+            w[b] = inm ? j_match_word<PFX>(o + jj - r, pos + x, pfx, P)
+                       : J_FINAL | (staged ? (uint32_t)slit[q] : lsrc ? (uint32_t)lsrc[lp + (x - a)] : lfill);
           }
         }
         j_store_words(st + pos + x0, w, x1 - x0);
@@ -5560,7 +5605,7 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
               w[b] = J_FINAL | (lsrc ? (uint32_t)lsrc[lp + rel] : lfill);
             } else {
               const uint32_t jj = rel - l;     // distance: o, or o times the periods passed
-              w[b] = o + (jj < o ? 0u : jj - jj % o);
+              w[b] = j_match_word<PFX>(o + (jj < o ? 0u : jj - jj % o), pos + x, pfx, P);
             }
           }
         }
@@ -6215,9 +6260,16 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     hipLaunchKernelGGL(zd_k_jsum_blocks, dim3((a.n_jblk + 63) / 64), dim3(64), 0, s, (const FrameState*)fstate,
                        blocks, comp, (const CompState*)cstate, jframes, jd, a.n_jblk, jb, jseg);
     hipLaunchKernelGGL(zd_k_jprefix, dim3(a.n_jframes), dim3(64 * JP_WAVES), 0, s, frames, fstate, jframes, jd, jb);
-    hipLaunchKernelGGL(zd_k_jscatter, dim3(a.n_jseg), dim3(64), 0, s, a.src, fstate, blocks, comp,
-                       (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
-                       (const uint16_t*)fses, jframes, jd, (const JBlk*)jb, (const JSeg*)jseg, jsd, jst);
+    if (R.k4 == K4_PREFIX)                     // each frame's own prefix, as the streaming launch above reads it
+      hipLaunchKernelGGL(zd_k_jscatter<true>, dim3(a.n_jseg), dim3(64), 0, s, a.src, fstate, blocks, comp,
+                         (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
+                         (const uint16_t*)fses, jframes, jd, (const JBlk*)jb, (const JSeg*)jseg, jsd, jst, frames,
+                         (const uint8_t* const*)(ws + W.dict_ptrs));
+    else
+      hipLaunchKernelGGL(zd_k_jscatter<false>, dim3(a.n_jseg), dim3(64), 0, s, a.src, fstate, blocks, comp,
+                         (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
+                         (const uint16_t*)fses, jframes, jd, (const JBlk*)jb, (const JSeg*)jseg, jsd, jst,
+                         (const FrameDesc*)nullptr, (const uint8_t* const*)nullptr);
     const uint64_t gw = (a.j_pieces + 16 * JW_K - 1) / (16 * JW_K);   // pieces per workgroup sweep
     const uint64_t gmax = 8ull * a.cus;                              // what fits at once: 8 workgroups per CU
     const dim3 gr((uint32_t)(gw < gmax ? (gw + 7) & ~7ull : (gmax + 7) & ~7ull));   // a multiple of 8 (one eighth per XCD)
@@ -6399,7 +6451,7 @@ __device__ uint64_t walk_scan(const uint8_t* __restrict__ src, uint64_t n, uint6
 template <bool FILL>
 __global__ __launch_bounds__(64) void zd_k_walk(const uint8_t* __restrict__ src, uint64_t n, uint64_t first,
                                                uint64_t chunk, uint32_t nranges, WalkRange* wr,
-                                               HostFrame* frames, HostBlock* blocks) {
+                                               HostFrame* frames, HostBlock* blocks, uint32_t wopt) {
   const uint32_t k = blockIdx.x;
   const int lane = threadIdx.x;
   if (k >= nranges) return;
@@ -6413,7 +6465,7 @@ __global__ __launch_bounds__(64) void zd_k_walk(const uint8_t* __restrict__ src,
     WalkFill sink{blocks, R.b_off};
     for (uint32_t f = 0; f < R.nframes; f++) {
       HostFrame hf;
-      index_frame(src, in, &hf, sink);
+      index_frame(src, in, &hf, sink, wopt);
       frames[R.f_off + f] = hf;
     }
     return;
@@ -6439,7 +6491,7 @@ __global__ __launch_bounds__(64) void zd_k_walk(const uint8_t* __restrict__ src,
       WalkCount sink;
       while (in.n && (uint64_t)(in.p - src) < hi) {
         HostFrame hf;
-        const int r = index_frame(src, in, &hf, sink);
+        const int r = index_frame(src, in, &hf, sink, wopt);
         nf++;
         if (r) { st = r; break; }
       }
@@ -6589,12 +6641,14 @@ hipError_t launch_plan_fill(const PlanCtx& X, const HostFrame* frames, const Hos
 }
 
 hipError_t launch_walk(const uint8_t* src, uint64_t n, uint64_t first, uint64_t chunk, uint32_t nranges, WalkRange* wr,
-                       HostFrame* frames, HostBlock* blocks, bool fill, hipStream_t s) {
+                       HostFrame* frames, HostBlock* blocks, bool fill, hipStream_t s, uint32_t wopt) {
   if (!nranges) return hipSuccess;
   if (fill)
-    hipLaunchKernelGGL(zd_k_walk<true>, dim3(nranges), dim3(64), 0, s, src, n, first, chunk, nranges, wr, frames, blocks);
+    hipLaunchKernelGGL(zd_k_walk<true>, dim3(nranges), dim3(64), 0, s, src, n, first, chunk, nranges, wr, frames, blocks,
+                       wopt);
   else
-    hipLaunchKernelGGL(zd_k_walk<false>, dim3(nranges), dim3(64), 0, s, src, n, first, chunk, nranges, wr, frames, blocks);
+    hipLaunchKernelGGL(zd_k_walk<false>, dim3(nranges), dim3(64), 0, s, src, n, first, chunk, nranges, wr, frames, blocks,
+                       wopt);
   return hipGetLastError();
 }
 
@@ -6664,7 +6718,7 @@ hipError_t launch_gather(const ChunkList& L, uint8_t* gathered, const GatherPiec
 // keeps; fill pass: one HostFrame per chunk and its blocks at b_off[i].
 template <bool FILL>
 __global__ __launch_bounds__(64) void zd_k_walk_chunks(const uint8_t* __restrict__ gathered, ChunkList L, uint32_t n,
-                                                      bool rfc_empty_lits, uint32_t* nblocks,
+                                                      uint32_t wopt, uint32_t* nblocks,
                                                       const uint64_t* __restrict__ b_off, HostFrame* frames,
                                                       HostBlock* blocks) {
   const uint32_t i = blockIdx.x * 64 + threadIdx.x;
@@ -6673,25 +6727,25 @@ __global__ __launch_bounds__(64) void zd_k_walk_chunks(const uint8_t* __restrict
   HostFrame hf;
   if (FILL) {
     WalkFill sink{blocks, b_off[i]};
-    index_chunk(gathered, in, &hf, sink, rfc_empty_lits);
+    index_chunk(gathered, in, &hf, sink, wopt);
     frames[i] = hf;
   } else {
     WalkCount sink;
-    index_chunk(gathered, in, &hf, sink, rfc_empty_lits);
+    index_chunk(gathered, in, &hf, sink, wopt);
     nblocks[i] = sink.n;
   }
 }
 
-hipError_t launch_walk_chunks(const uint8_t* gathered, const ChunkList& L, uint32_t n, bool rfc_empty_lits,
+hipError_t launch_walk_chunks(const uint8_t* gathered, const ChunkList& L, uint32_t n, uint32_t wopt,
                               uint32_t* nblocks, const uint64_t* b_off, HostFrame* frames, HostBlock* blocks, bool fill,
                               hipStream_t s) {
   if (!n) return hipSuccess;
   const dim3 grid((n + 63) / 64);
   if (fill)
-    hipLaunchKernelGGL(zd_k_walk_chunks<true>, grid, dim3(64), 0, s, gathered, L, n, rfc_empty_lits, nblocks, b_off,
+    hipLaunchKernelGGL(zd_k_walk_chunks<true>, grid, dim3(64), 0, s, gathered, L, n, wopt, nblocks, b_off,
                        frames, blocks);
   else
-    hipLaunchKernelGGL(zd_k_walk_chunks<false>, grid, dim3(64), 0, s, gathered, L, n, rfc_empty_lits, nblocks, b_off,
+    hipLaunchKernelGGL(zd_k_walk_chunks<false>, grid, dim3(64), 0, s, gathered, L, n, wopt, nblocks, b_off,
                        frames, blocks);
   return hipGetLastError();
 }
@@ -7051,7 +7105,7 @@ __global__ __launch_bounds__(256) void zd_k_batch_pack(const HostFrame* __restri
 // [src, src + size) (zd_walk.h chunk_size_query).
 __global__ __launch_bounds__(64) void zd_k_chunk_sizes(const uint64_t* __restrict__ src,
                                                       const uint64_t* __restrict__ size, uint32_t n,
-                                                      bool rfc_empty_lits, uint64_t* out_size, int32_t* status,
+                                                      uint32_t wopt, uint64_t* out_size, int32_t* status,
                                                       uint8_t* exact) {
   const uint32_t i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
@@ -7061,7 +7115,7 @@ __global__ __launch_bounds__(64) void zd_k_chunk_sizes(const uint64_t* __restric
   int st = 0;
   if ((!s && z) || s + z < s) st = ZD_E_INVALID_ARG;
   else if (z >= (1ull << 32)) st = ZD_E_OUT_OF_DOMAIN;
-  else if (z) st = chunk_size_query((const uint8_t*)(uintptr_t)s, (size_t)z, rfc_empty_lits, &r, &ex);
+  else if (z) st = chunk_size_query((const uint8_t*)(uintptr_t)s, (size_t)z, wopt, &r, &ex);
   out_size[i] = r;
   if (status) status[i] = st;
   if (exact) exact[i] = ex;
@@ -7075,10 +7129,10 @@ hipError_t launch_batch_pack(const HostFrame* frames, const HostBlock* blocks, c
   return hipGetLastError();
 }
 
-hipError_t launch_chunk_sizes(const uint64_t* src, const uint64_t* size, uint32_t n, bool rfc_empty_lits,
+hipError_t launch_chunk_sizes(const uint64_t* src, const uint64_t* size, uint32_t n, uint32_t wopt,
                               uint64_t* out_size, int32_t* status, uint8_t* exact, hipStream_t s) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(zd_k_chunk_sizes, dim3((n + 63) / 64), dim3(64), 0, s, src, size, n, rfc_empty_lits, out_size,
+  hipLaunchKernelGGL(zd_k_chunk_sizes, dim3((n + 63) / 64), dim3(64), 0, s, src, size, n, wopt, out_size,
                      status, exact);
   return hipGetLastError();
 }

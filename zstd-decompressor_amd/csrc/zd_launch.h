@@ -93,7 +93,7 @@ struct WalkRange;
 struct HostFrame;
 struct HostBlock;
 hipError_t launch_walk(const uint8_t* src, uint64_t n, uint64_t first, uint64_t chunk, uint32_t nranges, WalkRange* wr,
-                       HostFrame* frames, HostBlock* blocks, bool fill, hipStream_t s);
+                       HostFrame* frames, HostBlock* blocks, bool fill, hipStream_t s, uint32_t wopt = 0);
 
 // Device descriptors (zd_plan_create_device): the shape pass (PlanShape
 // zeroed first), the count pass + exclusive scan (cnt: nf x PLAN_FIELDS
@@ -122,7 +122,7 @@ hipError_t launch_gather(const ChunkList& L, uint8_t* gathered, const GatherPiec
 // zd_k_walk_chunks: one lane per chunk of the gathered buffer.  Count pass
 // (fill = false): nblocks[i] = the blocks chunk i's walk keeps; fill pass:
 // frames[i] and its blocks at blocks[b_off[i]...] (block indices global).
-hipError_t launch_walk_chunks(const uint8_t* gathered, const ChunkList& L, uint32_t n, bool rfc_empty_lits,
+hipError_t launch_walk_chunks(const uint8_t* gathered, const ChunkList& L, uint32_t n, uint32_t wopt,
                               uint32_t* nblocks, const uint64_t* b_off, HostFrame* frames, HostBlock* blocks, bool fill,
                               hipStream_t s);
 // zd_k_batch_results: chunk i's status and length from frame i's state (bind[i]:
@@ -194,7 +194,7 @@ hipError_t launch_batch_pack(const HostFrame* frames, const HostBlock* blocks, c
                              uint32_t align, uint64_t* cap, uint64_t* out, hipStream_t s);
 // zd_k_chunk_sizes: one lane per chunk, read in place: reserve, walk status and
 // exact flag per chunk (status / exact may be null).
-hipError_t launch_chunk_sizes(const uint64_t* src, const uint64_t* size, uint32_t n, bool rfc_empty_lits,
+hipError_t launch_chunk_sizes(const uint64_t* src, const uint64_t* size, uint32_t n, uint32_t wopt,
                               uint64_t* out_size, int32_t* status, uint8_t* exact, hipStream_t s);
 // zd_k_gather over the scanned piece starts instead of a piece list
 hipError_t launch_gather_scan(const ChunkList& L, uint8_t* gathered, const uint64_t* d_piece0, uint32_t n,

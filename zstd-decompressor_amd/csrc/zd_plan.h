@@ -108,7 +108,9 @@ struct PlanCtx {
   // else; `dict` is set with it, never `dset`): frame fi decodes against its own
   // raw-content prefix of prefix_bytes[fi] bytes (0: none) -- out_len0 is that
   // size, the first repeat offsets are 1, 4, 8, there are no previous tables,
-  // and a frame that names a Dictionary_ID is ZD_E_DICT_MISMATCH.
+  // and a frame that names a Dictionary_ID is ZD_E_DICT_MISMATCH.  With
+  // k4j_mode 1 (a batch created with ZD_F_BLOCK_PARALLEL, no chain: zd_route.h
+  // k4j_mode_behind) every such frame with a compressed block goes to K4J.
   const uint64_t* prefix_bytes;
 };
 
@@ -309,8 +311,14 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   // a prefix the streaming K4's int32 positions cannot hold (with the frame's
   // capacity, sequences or not: the frame starts at the prefix's size): no
   // block of the frame runs, and a size past the limit itself is not even kept
-  // (K4 truncates out_len0 to 32 bits)
-  if (X.prefix_bytes && out_len0 && (out_len0 > K4_MAX_FRAME_OUT || cap + out_len0 > K4_MAX_FRAME_OUT)) {
+  // (K4 truncates out_len0 to 32 bits).  A frame that a prefix batch created
+  // with ZD_F_BLOCK_PARALLEL sends to K4J keeps only the prefix's own limit:
+  // K4J's state words number the frame's own bytes from 0 and never hold a
+  // prefix position
+  const bool j_pfx = X.prefix_bytes && X.k4j_mode == 1 && !frame_failed_host && fd.nblocks && hf.ncomp &&
+                     hf.d.kind == ZD_FRAME_ZSTD && cap <= K4J_MAX_FRAME_OUT;
+  if (X.prefix_bytes && out_len0 &&
+      (out_len0 > K4_MAX_FRAME_OUT || (!j_pfx && cap + out_len0 > K4_MAX_FRAME_OUT))) {
     fs.key = plan_min(fs.key, make_key(PH_LIMIT, 0, 0, 0, ZD_E_OUT_OF_DOMAIN));
     fd.nblocks = 0;
     if (out_len0 > K4_MAX_FRAME_OUT) fd.out_len0 = out_len0 = 0;
@@ -318,8 +326,9 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   fd.out = out;
   fd.out_cap = cap;
   // K4J: frames of many compressed blocks, and any frame past the streaming
-  // K4's int32 positions (distances, zd_common.h)
-  const bool to_j = out_len0 == 0 && !frame_failed_host && fd.nblocks && hf.ncomp && hf.d.kind == ZD_FRAME_ZSTD &&
+  // K4's int32 positions (distances, zd_common.h); behind a prefix only on
+  // request (j_pfx: the scatter writes the bytes that come from the prefix)
+  const bool to_j = (out_len0 == 0 || j_pfx) && !frame_failed_host && fd.nblocks && hf.ncomp && hf.d.kind == ZD_FRAME_ZSTD &&
                     cap <= K4J_MAX_FRAME_OUT &&
                     (X.k4j_mode >= 0 ? X.k4j_mode == 1
                                      : ((X.k4j_auto && hf.ncomp >= X.k4j_min) || cap > K4_MAX_FRAME_OUT));

@@ -91,6 +91,12 @@ struct RouteEnv {
 inline int k4j_mode_of(uint32_t flags, const RouteEnv& E) {
   return (flags & ZD_F_BLOCK_PARALLEL) ? 1 : (flags & ZD_F_FRAME_SERIAL) ? 0 : E.k4j;
 }
+// The mode of a plan whose frames decode behind a dictionary, a dictionary set
+// or prefixes (`dict`): the streaming executor only, but for a prefix batch
+// (`prefix`) that is no chain and was created with ZD_F_BLOCK_PARALLEL
+inline int k4j_mode_behind(int mode, uint32_t flags, bool dict, bool prefix, bool chain) {
+  return !dict ? mode : (prefix && !chain && (flags & ZD_F_BLOCK_PARALLEL) && mode == 1) ? 1 : 0;
+}
 
 // What a plan is built for (plan_ctx).  `in` as route_plan's, its `context` set
 // for a dictionary or dictionary-set plan too (`dict`): the streaming executor only.

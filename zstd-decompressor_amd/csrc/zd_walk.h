@@ -220,8 +220,11 @@ ZD_HD inline int parse_header(Bytes& in, zd_frame_desc* f) {
 // Walks one frame at in, handing its blocks to the sink (S.size(): blocks
 // so far; S.push(block)).  On error, hf->key/status hold the failure; the
 // blocks parsed before (and the failing one, with its host_stage) are kept.
+// wopt: WALK_RFC_EMPTY_LITS (parse_compressed's rfc_empty_lits) and
+// WALK_LONG_WINDOW (ZD_F_LONG_WINDOW: a Window_Size up to MAX_WIN_SIZE_LONG,
+// 2 GiB, where the reference's MAX_WIN_SIZE stands otherwise).
 template <typename SINK>
-ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK& S, bool rfc_empty_lits = false) {
+ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK& S, uint32_t wopt = 0) {
   zd_frame_desc& f = hf->d;
   zero_bytes(&f, sizeof f);
   f.src_offset = (uint64_t)(in.p - base);
@@ -249,7 +252,8 @@ ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK
   if (f.magic == MAGIC_ZSTD) {
     f.kind = ZD_FRAME_ZSTD;
     if (int r = parse_header(in, &f)) return fail(r, 0, PS_STRUCT);
-    if (f.window_size > MAX_WIN_SIZE) return fail(ZD_E_WINDOW_SIZE_TOO_BIG, 0, PS_STRUCT);
+    if (f.window_size > ((wopt & WALK_LONG_WINDOW) ? MAX_WIN_SIZE_LONG : MAX_WIN_SIZE))
+      return fail(ZD_E_WINDOW_SIZE_TOO_BIG, 0, PS_STRUCT);
     for (uint32_t bi = 0;; bi++) {
       const uint8_t* h;
       if (int r = in.slice(3, &h)) return fail(r, bi, PS_STRUCT);
@@ -279,7 +283,7 @@ ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK
         cb.block_in_frame = bi;
         cb.host_stage = PS_ALL;
         WalkErr e;
-        int r = parse_compressed(base, hb.src, hb.size, &cb, &e, rfc_empty_lits);
+        int r = parse_compressed(base, hb.src, hb.size, &cb, &e, (wopt & WALK_RFC_EMPTY_LITS) != 0);
         if (r) {
           cb.host_stage = (uint8_t)e.stage;
           push(hb);
@@ -333,7 +337,7 @@ struct NoBlocks {
 // (trailing bytes, a truncated frame), ZD_E_OUT_OF_DOMAIN at a second zstd
 // frame -- and travels as hf->key, the route of a frame that fails to index.
 template <typename SINK>
-ZD_HD inline int index_chunk(const uint8_t* base, Bytes& in, HostFrame* hf, SINK& S, bool rfc_empty_lits = false) {
+ZD_HD inline int index_chunk(const uint8_t* base, Bytes& in, HostFrame* hf, SINK& S, uint32_t wopt = 0) {
   zero_bytes(&hf->d, sizeof hf->d);
   hf->d.src_offset = (uint64_t)(in.p - base);
   hf->d.content_size = UINT64_MAX;
@@ -355,13 +359,13 @@ ZD_HD inline int index_chunk(const uint8_t* base, Bytes& in, HostFrame* hf, SINK
                                     ((uint32_t)in.p[3] << 24)) == MAGIC_ZSTD;
     if (zstd) {
       if (have) return fail(ZD_E_OUT_OF_DOMAIN);
-      if (int r = index_frame(base, in, hf, S, rfc_empty_lits)) return r;
+      if (int r = index_frame(base, in, hf, S, wopt)) return r;
       have = true;
     } else {
       // a skippable frame, or the walk's own failure (bytes that are no frame)
       HostFrame skip;
       NoBlocks none;
-      if (int r = index_frame(base, in, &skip, none, rfc_empty_lits)) return fail(r);
+      if (int r = index_frame(base, in, &skip, none, wopt)) return fail(r);
     }
   }
   return 0;
@@ -426,12 +430,12 @@ struct WalkBound {
 // (base = in.p = src, so every read is inside the chunk: Bytes is bounds-checked
 // and index_chunk peeks four bytes only when four are left), the walk's status
 // and the reserve.
-ZD_HD inline int chunk_size_query(const uint8_t* src, size_t size, bool rfc_empty_lits, uint64_t* reserve,
+ZD_HD inline int chunk_size_query(const uint8_t* src, size_t size, uint32_t wopt, uint64_t* reserve,
                                   uint8_t* exact) {
   Bytes in{src, size};
   HostFrame hf;
   WalkBound sink;
-  const int st = index_chunk(src, in, &hf, sink, rfc_empty_lits);
+  const int st = index_chunk(src, in, &hf, sink, wopt);
   *reserve = chunk_reserve(hf, sink.bound, exact);
   return st;
 }

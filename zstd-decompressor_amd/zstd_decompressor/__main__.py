@@ -1,7 +1,7 @@
 """Command line, mirroring the reference CLI (src/main.rs:7-60):
 
-    python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]... [--verify]
-    python -m zstd_decompressor FILE --patch-from OLD -o FILE
+    python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]... [--verify] [--long]
+    python -m zstd_decompressor FILE --patch-from OLD -o FILE [--long]
 
 Decodes every frame of FILE on the GPU (the HIP pipeline behind zd_decompress)
 and writes the concatenated output to stdout or --output.  As in the
@@ -23,7 +23,14 @@ without an ID with the one raw-content file if there is one, else the first.
 against the bytes of OLD as its prefix (raw content, whatever they start
 with): a prefix batch of one chunk with OLD uploaded.  The output is written
 as bytes (a patched file need not be text); a failure prints the chunk's
-status name and exits with status 1.  Not together with -D.
+status name and exits with status 1.  Not together with -D.  A frame whose
+Frame_Content_Size is at least 2 MiB (16 blocks of 128 KiB, the block count
+from which a plain plan sends a frame to the block-parallel executor) is
+decoded block-parallel (F_BLOCK_PARALLEL); a smaller one, or one without a
+Frame_Content_Size, on the streaming executor.
+--long accepts frames whose Window_Size is up to 2 GiB (F_LONG_WINDOW; the
+default is the reference's 8 MiB limit): what `zstd --long` and `zstd
+--patch-from` write for inputs past 8 MiB.
 """
 from __future__ import annotations
 
@@ -31,7 +38,11 @@ import argparse
 import sys
 
 from . import _lib
-from .batch import Dictionary, DictionarySet, Plan, decode_tensors, frames_index
+from .batch import Dictionary, DictionarySet, Plan, chunk_sizes, decode_tensors, frames_index
+
+# --patch-from: a frame of at least this Frame_Content_Size goes to the block-parallel executor (K4J_MIN_BLOCKS
+# blocks of 128 KiB, zd_plan.h: the plain plans' own threshold in bytes the command line can see)
+PATCH_BLOCK_PARALLEL_BYTES = 16 * (128 << 10)
 
 
 def _info(data: bytes) -> int:
@@ -72,6 +83,9 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--patch-from", dest="patch_from", metavar="old",
                     help="decode the one frame of the input against this file as its prefix, as zstd --patch-from "
                          "(not in the reference; not together with -D)")
+    ap.add_argument("--long", dest="long_window", action="store_true",
+                    help="accept frames whose Window_Size is up to 2 GiB (default: 8 MiB, the reference's limit), "
+                         "as written by zstd --long and by --patch-from on large files (not in the reference)")
     return ap
 
 
@@ -80,18 +94,29 @@ def _patch(a, data: bytes) -> int:
     Frame_Content_Size, else by 128 KiB per block (what a batch reserves)."""
     import torch
     old = open(a.patch_from, "rb").read()
-    frames, blocks, st, _ = frames_index(data)
-    cap = 0
-    for f in frames:
-        if f["kind"] == 1:
-            continue
-        cs = f["content_size"]
-        cap = max(cap, cs if cs != (1 << 64) - 1 else (128 << 10) * max(f["num_blocks"], 1))
     dev = torch.device("cuda", torch.cuda.current_device())
     up = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) if b else torch.empty(0, dtype=torch.uint8, device=dev)
+    d_src = up(data)
+    cap, fcs = 0, None
+    if a.long_window:
+        # (the host index takes no flags: the device's size query walks the chunk under the long limit, and as a
+        # prefix batch walks it: an empty Raw literals section is accepted)
+        sizes, _, exact = chunk_sizes([d_src.data_ptr()], [len(data)], dictionary=True, long_window=True)
+        cap = int(sizes.cpu()[0])
+        fcs = cap if int(exact.cpu()[0]) else None
+    else:
+        frames, blocks, st, _ = frames_index(data)
+        for f in frames:
+            if f["kind"] == 1:
+                continue
+            cs = f["content_size"]
+            fcs = cs if cs != (1 << 64) - 1 else None
+            cap = max(cap, cs if fcs is not None else (128 << 10) * max(f["num_blocks"], 1))
     d_dst = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-    flags = _lib.F_VERIFY_CHECKSUM if a.verify else 0
-    status, length = decode_tensors([up(data)], [d_dst], flags=flags, prefixes=[up(old)])
+    flags = (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0)
+    if fcs is not None and fcs >= PATCH_BLOCK_PARALLEL_BYTES:
+        flags |= _lib.F_BLOCK_PARALLEL
+    status, length = decode_tensors([d_src], [d_dst], flags=flags, prefixes=[up(old)])
     if status[0] != 0:
         print(f"Error: {_lib.status_name(status[0])}", file=sys.stderr)
         return 1
@@ -131,7 +156,9 @@ def main(argv=None) -> int:
     except _lib.ZdError as e:
         print(f"Error: dictionary: {e.name}", file=sys.stderr)
         return 1
-    plan = Plan(data, a.print_skippable, _lib.F_VERIFY_CHECKSUM if a.verify else 0, dictionary=dictionary)
+    plan = Plan(data, a.print_skippable,
+                (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0),
+                dictionary=dictionary)
     dev = torch.device("cuda", torch.cuda.current_device())
     d_src = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
     if data:

@@ -262,7 +262,7 @@ CHECKSUM_WRONG = -100  # F_VERIFY_CHECKSUM: the frame decoded, its bytes do not 
 DICT_SET_MAX = 4096    # ZD_DICT_SET_MAX
 CHAIN_MAX_DEPTH = 255  # ZD_CHAIN_MAX_DEPTH: in-batch ancestors a chunk of a chain batch may have
 F_SKIPPABLE = 1
-F_BLOCK_PARALLEL = 2   # every frame with a compressed block -> K4J (block-parallel execute)
+F_BLOCK_PARALLEL = 2   # every frame with a compressed block -> K4J (block-parallel execute); prefix batches too
 F_FRAME_SERIAL = 4     # no frame -> K4J
 F_SEQ_ONE_LANE = 8     # K3 one lane per block instead of four (K3Q)
 F_NO_FUSE = 32         # K3 then K4 as two launches in few-frame plans (no zd_k_fused)
@@ -271,5 +271,7 @@ F_J_ONE_ROUND = 128    # test switch: K4J pointer jumping cut to one round of on
 F_SEQ_NO_LATENCY = 256 # K3Q instead of the one-block-per-wave K3L in plans of few blocks
 F_K1_SPLIT = 512       # K1 as a parse pass and a build pass in a plan of any size
 F_VERIFY_CHECKSUM = 1024  # Content_Checksums verified inside the decode launch (zd_k_verify): CHECKSUM_WRONG
+F_LONG_WINDOW = 2048   # accept a Window_Size up to 2 GiB (default: the reference's 8 MiB limit)
 SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
+SIZES_LONG_WINDOW = 2048  # zd_chunk_sizes_device: the chunks will be decoded with F_LONG_WINDOW (the same bit)
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)

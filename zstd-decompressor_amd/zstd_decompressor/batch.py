@@ -299,7 +299,7 @@ def _device_arrays(arrs, nchunks, lists=True):
     return n, addr, keep
 
 
-def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, stream=None):
+def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, stream=None, long_window: bool = False):
     """zd_chunk_sizes_device: what each chunk needs of its destination, asked
     on the device.  src_ptrs / src_sizes as in Batch.from_device (device
     tensors, or addresses with `nchunks`).  Returns three device tensors
@@ -307,8 +307,9 @@ def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, str
     Frame_Content_Size, exact 1, else 128 KiB per compressed block + its raw
     and RLE blocks, exact 0; 0 for a failing or empty chunk) and the status of
     its header walk.  dictionary=True when the chunks will be decoded with a
-    Dictionary or DictionarySet.  The kernel is queued on `stream` (torch's
-    current stream by default) and nothing is synchronised."""
+    Dictionary or DictionarySet, long_window=True when with F_LONG_WINDOW (a
+    Window_Size up to 2 GiB is then no failure).  The kernel is queued on
+    `stream` (torch's current stream by default) and nothing is synchronised."""
     import torch
     if stream is None:
         stream = torch.cuda.current_stream().cuda_stream
@@ -319,7 +320,8 @@ def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, str
     exact = torch.empty(n, dtype=torch.uint8, device=dev)
     ptr = lambda t: C.c_void_p(t.data_ptr() if n else 0)
     _lib.check(_lib.lib().zd_chunk_sizes_device(C.c_void_p(addr[0]), C.c_void_p(addr[1]), n,
-                                                _lib.SIZES_DICT if dictionary else 0, ptr(sizes), ptr(statuses),
+                                                (_lib.SIZES_DICT if dictionary else 0) |
+                                                (_lib.SIZES_LONG_WINDOW if long_window else 0), ptr(sizes), ptr(statuses),
                                                 ptr(exact), C.c_void_p(stream)), "zd_chunk_sizes_device")
     return sizes, statuses, exact
 
