@@ -154,7 +154,8 @@ typedef struct zd_plan zd_plan;
 /* Executor choice for frames of many blocks; default:
  * automatic.  Same output either way; tests run both.  Plans with a
  * dictionary or a dictionary set, chain batches and zd_context ignore both
- * flags (the streaming executor only); a prefix batch (zd_batch_create_prefix,
+ * flags (the streaming executor only; a chain batch has a flag of its own,
+ * ZD_F_CHAIN_BLOCK_PARALLEL); a prefix batch (zd_batch_create_prefix,
  * zd_batch_create_device_prefix) ignores the automatic rule and takes K4J only
  * when ZD_F_BLOCK_PARALLEL asks for it: large deltas, whose hundreds of blocks
  * one wave would decode one after another. */
@@ -227,6 +228,21 @@ typedef struct zd_plan zd_plan;
  * window, each checks an offset against the bytes produced so far.  Without
  * the flag nothing changes.  zd_context keeps its own window check. */
 #define ZD_F_LONG_WINDOW 2048u
+/* A chain batch on the block-parallel executor (zd_batch_create_chain,
+ * zd_batch_create_device_chain; opt-in, large deltas): every chunk whose frame
+ * has a compressed block executes on K4J, level by level, whether or not it has
+ * a parent and whether its prefix is external, a parent's output or none;
+ * frames without a compressed block stay on zd_k_execute_chain, and
+ * zd_batch_info.executors carries ZD_EXEC_K4J.  The same bytes, statuses and
+ * lengths as the batch gives without the flag, with the one exception a prefix
+ * batch created with ZD_F_BLOCK_PARALLEL has: a K4J frame needs its prefix to
+ * fit 0x7FFF0000 bytes and its capacity K4J's 32 GiB, not the two together to
+ * fit 0x7FFF0000.  A chain batch keeps ignoring ZD_F_BLOCK_PARALLEL and
+ * ZD_F_FRAME_SERIAL.  Everywhere else the flag is accepted and ignored: plain,
+ * dictionary and prefix batches, zd_plan_*, zd_decompress*, the sharded calls.
+ * K4J is several times slower than the streaming executor on small frames
+ * (16 KiB pages; README), which is why no rule sets this flag by itself. */
+#define ZD_F_CHAIN_BLOCK_PARALLEL 4096u
 
 /* zd_plan_info.executors: */
 #define ZD_EXEC_FUSED 1u   /* zd_k_fused: tables, FSE chains and execution per group of four
@@ -732,7 +748,18 @@ int  zd_batch_create_device_prefix(const void* const* d_src_ptrs, const uint64_t
  *    a parent outside [-1, nchunks); parent[i] == i; a cycle; a chunk with more
  *    than ZD_CHAIN_MAX_DEPTH ancestors; prefix_bytes[i] != 0 on a chunk with a
  *    parent.  nchunks == 0 is ZD_OK.
- * Everything else is a prefix batch's: the streaming executor only, no
+ *  - ZD_F_CHAIN_BLOCK_PARALLEL (large deltas, a checkpoint shard patched every
+ *    step): the frames with a compressed block execute on K4J instead.  Per
+ *    level, in level order on the stream: zd_k_execute_chain over the level's
+ *    frames, then K4J's scatter over the level's segments and its
+ *    pointer-jumping rounds over the level's pieces -- still no workgroup that
+ *    waits for another.  A chunk whose pointer jumping does not converge shows
+ *    ZD_E_OUT_OF_DOMAIN in zd_batch_device_results and its descendants
+ *    ZD_E_NOT_DECODED until zd_batch_results, which decodes that chunk and every
+ *    chunk behind it again on the streaming executor (one internal chain batch)
+ *    and updates the device arrays.
+ * Everything else is a prefix batch's: the streaming executor only (but for
+ * ZD_F_CHAIN_BLOCK_PARALLEL; ZD_F_BLOCK_PARALLEL is ignored), no
  * dictionary or set, not packed, ZD_F_SKIPPABLE refused, the sources gathered
  * at creation, zd_batch_decode_async free of allocation and host
  * synchronisation, capturable and re-launchable; every zd_batch_* call works on

@@ -154,6 +154,18 @@ struct zd_plan {
   const uint32_t* d_chain_order = nullptr;
   const int32_t* d_chain_parent = nullptr;
   std::vector<uint32_t> chain_count;
+  // a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL (zd_route.h chain_j):
+  // its J frames are numbered level-major (zd_plan.h plan_j_order), chain_j[l]
+  // level l's ranges of K4J's grids.  What the planners need for that: the
+  // frames by level on the host (host arrays), or the batch's level counters on
+  // the device (device arrays; d_chain_order is order[] there)
+  std::vector<JLevel> chain_j;
+  std::vector<uint32_t> h_chain_order;
+  const uint32_t* d_chain_lcount = nullptr;
+  bool chain_on_j() const { return zd::chain_j(flags, chain); }
+  uint32_t jpend_words() const {
+    return chain_on_j() ? jpend_chain_words((uint32_t)chain_count.size()) : JPEND_WORDS;
+  }
   bool with_dict() const { return dict != nullptr || dset != nullptr || prefix; }
   // the walk's options (zd_walk.h): parse_compressed's rfc_empty_lits, ZD_F_LONG_WINDOW
   uint32_t walk_opts() const { return zd::walk_opts(with_dict(), (flags & ZD_F_LONG_WINDOW) != 0); }
@@ -422,7 +434,7 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   X.k4j_auto = X.k4j_mode < 0 && out_len0 == 0 && j_candidates > 0 && j_candidates <= K4J_MAX_FRAMES;
   if (X.dict) {
     X.k4j_auto = false;
-    X.k4j_mode = k4j_mode_behind(X.k4j_mode, P->flags, true, P->prefix, P->chain);
+    X.k4j_mode = k4j_mode_plan(X.k4j_mode, P->flags, true, P->prefix, P->chain);
   }
   return X;
 }
@@ -478,7 +490,7 @@ void carve_tail(zd_plan* P, Workspace& W, const PlanCounts& T, uint64_t& o, uint
   }
   W.jblk = carve(sizeof(JBlk) * std::max<uint64_t>(T.jblk, 1));
   W.jseg = carve(sizeof(JSeg) * std::max<uint64_t>(T.jseg, 1));
-  W.jpend = carve(4 * (J_MAX_ROUNDS + 1));
+  W.jpend = carve(4 * (uint64_t)P->jpend_words());
   W.jdone = carve(std::max<uint64_t>(j_pieces, 1));
   W.jst = carve(4 * P->j_bytes + 64);
   W.redo = carve(std::max<uint64_t>(T.frames, 1));
@@ -599,21 +611,31 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
         }
     plan_dict_comps(P, used.data());
   }
-  const PlanCtx X = plan_ctx(P, prev_huf, prev_tab, out_len0, rep0, fixed_cap, host_single_block_frames(P),
-                             j_candidates);
+  PlanCtx X = plan_ctx(P, prev_huf, prev_tab, out_len0, rep0, fixed_cap, host_single_block_frames(P), j_candidates);
 
   const size_t np = P->parts.size();
   std::vector<PlanCounts> cnt(np + 1);
   const uint32_t dict_comps = P->n_dict_comps;
   cnt[0].comps = cnt[0].luts = cnt[0].fses = dict_comps;
   const Sink none{};
+  // a chain batch on K4J: each frame's own K4J counts, for the level-major numbering below
+  const bool jlevels = P->chain_on_j() && X.place_out && P->h_chain_order.size() == P->nframes;
+  if (P->chain_on_j() && !jlevels && P->nframes) return ZD_E_INVALID_ARG;
+  std::vector<uint64_t> jcnt(jlevels ? PLAN_J_COLS * P->nframes : 0), j_at(jcnt.size());
   run_parts(np, [&](size_t k) {
     const HostPart& hp = P->parts[k];
     PlanCounts c;
     // (a batch's placement is by plan frame index: the part counts from its
     // first frame's, taken off again below)
     if (X.place_out) c.frames = P->part_f0[k];
-    for (const HostFrame& hf : hp.frames) plan_frame<false, JMax>(X, hf, hp.blocks.data(), c, none, nullptr);
+    for (const HostFrame& hf : hp.frames) {
+      uint64_t j0[PLAN_J_COLS], j1[PLAN_J_COLS];
+      const uint64_t fi = c.frames;
+      plan_j_get(c, j0);
+      plan_frame<false, JMax>(X, hf, hp.blocks.data(), c, none, nullptr);
+      plan_j_get(c, j1);
+      if (jlevels) for (int w = 0; w < PLAN_J_COLS; w++) jcnt[PLAN_J_COLS * fi + w] = j1[w] - j0[w];
+    }
     if (X.place_out) c.frames -= P->part_f0[k];
     if (X.fused) {          // parts start aligned, so the filling pass pads exactly as this count did
       c.lits = align_up(c.lits, 128);
@@ -623,6 +645,17 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
   });
   for (size_t k = 1; k <= np; k++) { PlanCounts t = cnt[k - 1]; t.add(cnt[k]); cnt[k] = t; }
   const PlanCounts T = cnt[np];
+  P->chain_j.clear();
+  if (jlevels) {
+    // the J frames level-major: every level owns one contiguous range of J
+    // frames, J blocks, segments, state words and pieces (the fill pass places
+    // each frame's K4J entries at j_at instead of the running counts)
+    uint64_t tot[PLAN_J_COLS];
+    P->chain_j.resize(P->chain_count.size());
+    plan_j_order(jcnt.data(), P->h_chain_order.data(), P->chain_count.data(), (uint32_t)P->chain_count.size(),
+                 j_at.data(), P->chain_j.data(), tot);
+    X.j_at = j_at.data();
+  }
 
   // workspace carve-up: the arrays the host fills first (one upload), then
   // the device-only ones
@@ -1108,6 +1141,12 @@ struct DevWalkBufs {                      // device and pinned buffers, kept bet
   PlanShape* d_shape = nullptr;
   uint64_t* h_small = nullptr;           // pinned: shape, totals
   uint32_t* h_chain = nullptr;           // pinned: a chain batch's level counts, cursors and links (BatchCarve::lcount)
+  // a chain batch on K4J (build_plan_device): the K4J columns in order[] order,
+  // their scan's scratch, the frames' places, the levels' first entries | the pinned copy of the last
+  uint64_t* d_jord = nullptr;
+  size_t cap_jord = 0;
+  uint64_t* h_jlev = nullptr;
+  size_t cap_jlev = 0;
 };
 DevWalkBufs& dev_walk_bufs() {
   static DevWalkBufs* b = new DevWalkBufs();
@@ -1347,13 +1386,38 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
       HIPCHK(hipMemcpy(in->d_dset, P->dset_tab.data(), P->dset_tab.size() * sizeof(PlanDict), hipMemcpyHostToDevice));
     X.dset = in->d_dset;
   }
-  HIPCHK(launch_plan_count(X, d_frames, d_blocks, F, B.d_cnt, B.d_tot, B.d_shape, s, P->n_dict_comps));
+  // a chain batch on K4J: the frames' K4J counts scanned in order[] order, so
+  // that the J frames are numbered level-major; the levels' first entries come
+  // back with the totals (no wait of their own)
+  const bool jlevels = P->chain_on_j() && F;
+  PlanJOrder jo{};
+  constexpr size_t JLEV_WORDS = 3 * CHAIN_LEVELS;
+  if (jlevels) {
+    if (!P->d_chain_order || !P->d_chain_lcount || !X.place_out) return ZD_E_INVALID_ARG;
+    // col | scratch | j_at | lev
+    const size_t col = PLAN_J_COLS * F, scr = PLAN_J_COLS * (nt + 1);
+    if (!grow_dev(B.d_jord, B.cap_jord, 2 * col + scr + JLEV_WORDS) || !grow_pinned(B.h_jlev, B.cap_jlev, JLEV_WORDS))
+      return ZD_E_HIP;
+    jo = PlanJOrder{P->d_chain_order, P->d_chain_lcount, B.d_jord, B.d_jord + col, B.d_jord + col + scr,
+                    B.d_jord + 2 * col + scr};
+    HIPCHK(hipMemsetAsync(jo.lev, 0, 8 * JLEV_WORDS, s));
+  }
+  HIPCHK(launch_plan_count(X, d_frames, d_blocks, F, B.d_cnt, B.d_tot, B.d_shape, s, P->n_dict_comps,
+                           jlevels ? &jo : nullptr));
   HIPCHK(hipMemcpyAsync(B.h_small, B.d_tot + nt * PLAN_FIELDS, PLAN_FIELDS * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(B.h_small + PLAN_FIELDS, B.d_shape, sizeof(PlanShape), hipMemcpyDeviceToHost, s));
+  if (jlevels) HIPCHK(hipMemcpyAsync(B.h_jlev, jo.lev, 8 * JLEV_WORDS, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   PlanCounts T;
   memcpy(&T, B.h_small, sizeof T);
   memcpy(&shape, B.h_small + PLAN_FIELDS, sizeof shape);
+  P->chain_j.clear();
+  if (jlevels) {
+    P->chain_j.resize(P->chain_count.size());
+    plan_j_levels(B.h_jlev, P->chain_count.data(), (uint32_t)P->chain_count.size(), T.jframes, T.jseg, T.jpieces,
+                  P->chain_j.data());
+    X.j_at = jo.j_at;
+  }
   Workspace& W = P->W;
   W = Workspace{};
   uint64_t o = 0;
@@ -1890,7 +1954,8 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
   // deep pool counters, K4J's round counters and done flags; ZD_RESET_COPIES
   // builds keep the six copy / fill launches it replaced)
 #ifndef ZD_RESET_COPIES
-  HIPCHK(launch_reset(P->d_ws, P->W, P->n_frames, P->n_comps, P->n_jframes != 0, P->j_pieces, s, P->n_dict_comps));
+  HIPCHK(launch_reset(P->d_ws, P->W, P->n_frames, P->n_comps, P->n_jframes != 0, P->j_pieces, s, P->n_dict_comps,
+                      P->jpend_words()));
 #else
   HIPCHK(hipMemcpyAsync(P->d_ws + P->W.frame_state, P->d_ws + P->W.frame_state0,
                         P->n_frames * sizeof(FrameState), hipMemcpyDeviceToDevice, s));
@@ -1898,7 +1963,7 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
   HIPCHK(hipMemsetAsync(P->d_ws + P->W.huge, 0, 4, s));
   HIPCHK(hipMemsetAsync(P->d_ws + P->W.deep, 0, 4, s));
   if (P->n_jframes) {
-    HIPCHK(hipMemsetAsync(P->d_ws + P->W.jpend, 0, 4 * (J_MAX_ROUNDS + 1), s));
+    HIPCHK(hipMemsetAsync(P->d_ws + P->W.jpend, 0, 4 * (size_t)P->jpend_words(), s));
     HIPCHK(hipMemsetAsync(P->d_ws + P->W.jdone, 0, std::max<uint64_t>(P->j_pieces, 1), s));
   }
 #endif
@@ -1930,6 +1995,8 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
     a.chain_parent = P->d_chain_parent;
     a.chain_count = P->chain_count.data();
     a.chain_levels = (uint32_t)P->chain_count.size();
+    if (P->chain_on_j() && P->chain_j.size() == P->chain_count.size()) a.chain_j = P->chain_j.data();
+    if (P->n_jframes && !a.chain_j) return ZD_E_INVALID_ARG;   // (never: a chain plan has J frames only level by level)
   }
   // (every plan has its second stream, aux_take, and a profiled one its events, zd_plan_set_profiling)
   if (((R.fork || R.k1_fork) && !P->aux) || (R.profiling && !P->ev_made)) return ZD_E_HIP;
@@ -2915,6 +2982,11 @@ static int batch_create(const BatchSpec& S, zd_batch** out) {
     P->d_chain_order = B->d_order;
     P->d_chain_parent = B->d_par;
     P->chain_count = B->chain_count;
+    // ZD_F_CHAIN_BLOCK_PARALLEL: what the planners number the J frames level-major from
+    if (P->chain_on_j()) {
+      if (S.on_device) P->d_chain_lcount = B->d_lcount;
+      else P->h_chain_order.assign(H.chain.begin() + n, H.chain.end());
+    }
   }
   DevPlanIn in;                            // device arrays
   std::unique_ptr<void, Free> set_mem;
@@ -3150,6 +3222,37 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
       if (key_code(k) == ZD_E_OUT_OF_DOMAIN && key_phase(k) == PH_LIMIT && key_stage(k) == LS_JROUNDS)
         redo.push_back(i);
     }
+    // a chain batch (K4J only with ZD_F_CHAIN_BLOCK_PARALLEL): every chunk behind
+    // such a chunk goes with it -- the launch left them ZD_E_NOT_DECODED -- as one
+    // streaming chain batch over that set, the parents remapped.  A chunk of the
+    // set whose parent is outside it (the parent decoded fine) is a root there:
+    // its prefix entry, the parent's destination and Frame_Content_Size or its
+    // own external prefix, goes with it as an external prefix.
+    std::vector<int64_t> rpar;
+    if (B->chain && !redo.empty()) {
+      std::vector<int32_t> par(n);
+      HIPCHK(hipMemcpy(par.data(), B->d_par, 4 * n, hipMemcpyDeviceToHost));
+      // in[i]: 1 in the set, 0 not, -1 unknown; every chunk walks up to a known ancestor
+      std::vector<int8_t> in(n, -1);
+      for (size_t i : redo) in[i] = 1;
+      std::vector<size_t> path;
+      for (size_t i = 0; i < n; i++) {
+        path.clear();
+        int64_t p = (int64_t)i;
+        while (p >= 0 && in[(size_t)p] < 0 && path.size() <= n) { path.push_back((size_t)p); p = par[(size_t)p]; }
+        const int8_t v = p >= 0 ? in[(size_t)p] : (int8_t)0;
+        for (size_t q : path) in[q] = v;
+      }
+      redo.clear();
+      std::vector<int64_t> at(n, -1);
+      for (size_t i = 0; i < n; i++)
+        if (in[i] == 1) { at[i] = (int64_t)redo.size(); redo.push_back(i); }
+      rpar.resize(redo.size());
+      for (size_t k = 0; k < redo.size(); k++) {
+        const int32_t p = par[redo[k]];
+        rpar[k] = p >= 0 ? at[(size_t)p] : -1;
+      }
+    }
     if (!redo.empty()) {
       if (int r = B->host_arrays()) return r;
       const size_t m = redo.size();
@@ -3166,8 +3269,8 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
       // a prefix batch (K4J only with ZD_F_BLOCK_PARALLEL): the redo chunks'
       // checked prefix addresses and sizes go with them -- a chunk whose prefix
       // plus capacity the streaming executor cannot hold ends ZD_E_OUT_OF_DOMAIN.
-      // (plan_ctx turns K4J off for every dictionary, set and chain plan, so
-      // such a batch never has n_jframes)
+      // (plan_ctx turns K4J off for every dictionary and set plan, so such a
+      // batch never has n_jframes; a chain batch: the roots' entries only)
       std::vector<const void*> pf;
       std::vector<uint64_t> pz;
       if (P->prefix) {
@@ -3179,14 +3282,16 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
         }
         pf.resize(m); pz.resize(m);
         for (size_t k = 0; k < m; k++) {
-          pz[k] = z[redo[k]];
+          // (a chunk whose parent is in the redo batch: the parent's output there, no external prefix)
+          pz[k] = (B->chain && rpar[k] >= 0) ? 0 : z[redo[k]];
           pf[k] = pz[k] ? (const void*)(uintptr_t)a[redo[k]] : nullptr;
         }
       }
       BatchSpec S{src.data(), sz.data(), dst.data(), dc.data()};
       if (P->prefix) { S.prefix = pf.data(); S.prefix_bytes = pz.data(); }
+      if (B->chain) { S.chain = true; S.parent = rpar.data(); }
       S.n = m;
-      S.flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_J_ONE_ROUND)) | ZD_F_FRAME_SERIAL;
+      S.flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_CHAIN_BLOCK_PARALLEL | ZD_F_J_ONE_ROUND)) | ZD_F_FRAME_SERIAL;
       S.dict = B->dict;
       S.dset = B->dset;
       S.stream = s;

@@ -5415,7 +5415,15 @@ __device__ __attribute__((always_inline)) inline uint32_t j_match_word(uint32_t 
 // (Workspace::dict_ptrs, as zd_k_execute_prefix reads it; both wave-uniform).
 // Without it the two arguments are never read and the kernel's instructions
 // are what they were before prefix batches came to K4J.
-template <bool PFX>
+// CHAIN (a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL, with PFX): the
+// grid covers one level's segments, seg0 its first; a frame's prefix is its
+// parent's output of a level below, final when this launch starts.  Before
+// any prefix byte is read the wave makes zd_k_execute_chain's parent check: a
+// parent with a key, or one that decoded to another length than the child was
+// planned with, keys the frame ZD_E_NOT_DECODED (key_min, the streaming
+// kernel's key), and the wave writes no word; zd_k_jround skips a keyed frame.
+// Without CHAIN the two arguments after pfx_ptrs are never read.
+template <bool PFX, bool CHAIN = false>
 __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ src, FrameState* fstate,
                                                     const BlockRec* __restrict__ blocks,
                                                     const CompBlock* __restrict__ comp,
@@ -5426,7 +5434,8 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
                                                     const JBlkDesc* __restrict__ jd, const JBlk* __restrict__ jb,
                                                     const JSeg* __restrict__ jseg, const JSegDesc* __restrict__ jsd,
                                                     uint32_t* jst, const FrameDesc* __restrict__ frames,
-                                                    const uint8_t* const* __restrict__ pfx_ptrs) {
+                                                    const uint8_t* const* __restrict__ pfx_ptrs,
+                                                    uint32_t seg0, const int32_t* __restrict__ parent) {
   __shared__ __attribute__((aligned(16))) uint8_t stab[3][FSE_TAB];
   __shared__ uint32_t sa[65], sll[64], soff[64], slp[64];
 #if ZD_JS_STAGE
@@ -5434,11 +5443,22 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
   l_u8* const slit = (l_u8*)slit_;
 #endif
   const int lane = threadIdx.x;
-  const JSegDesc SD = jsd[blockIdx.x];
+  const JSegDesc SD = jsd[CHAIN ? seg0 + blockIdx.x : blockIdx.x];
   const uint32_t e = SD.jblk;
   if (jb[e].dead) return;
   const JBlkDesc D = jd[e];
   const JFrame JF = jframes[D.jframe];
+  if constexpr (CHAIN) {
+    // (wave-uniform; every wave of the frame finds the same and writes the same key)
+    const int32_t p = parent[JF.frame];
+    if (p >= 0) {
+      const uint64_t pkey = fstate[p].key, plen = fstate[p].out_len;
+      if (pkey != KEY_NONE || plen != frames[JF.frame].out_len0) {
+        if (lane == 0) key_min(fstate, JF.frame, make_key(PH_PARSE, 0, PS_STRUCT, 0, ZD_E_NOT_DECODED));
+        return;
+      }
+    }
+  }
   uint32_t* st = jst + JF.base;
   const BlockRec B = blocks[D.block];
   uint64_t pos = jb[e].out_start;
@@ -5664,12 +5684,23 @@ constexpr int JW_K = ZD_JW_K;   // pieces per lane in flight (each hop issues JW
 // byte, and every chain ends at a literal the scatter wrote), so each wave
 // sweeps its own pieces until it leaves none pending, and the tail of empty
 // rounds costs one launch instead of one each.
+// LVL (a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL): the launch sweeps
+// one level's pieces, the n_pieces from the first piece of J frame jf0 (the
+// level's first) on; piece0, done[] and j_frame_of keep the plan's numbering,
+// and pend points at the level's own slots, so a level neither skips its
+// sweeps for an earlier level's empty count nor inherits one.  jf0 lies in
+// the four bytes of padding the arguments had before n_pieces: every other
+// argument, the hidden ones included, stays where it was, and without LVL it
+// is never read (zd_k_jround<false> has the instructions zd_k_jround had).
+template <bool LVL>
 __global__ __launch_bounds__(256) void zd_k_jround(uint8_t* outbase, const FrameDesc* __restrict__ frames,
                                                    FrameState* fstate, const JFrame* __restrict__ jframes,
-                                                   uint32_t n_jframes, uint64_t n_pieces, uint32_t* jst,
+                                                   uint32_t n_jframes, uint32_t jf0, uint64_t n_pieces, uint32_t* jst,
                                                    uint32_t* pend, uint8_t* done, uint32_t hops, uint32_t r,
                                                    uint32_t last, uint32_t sweeps) {
   if (r > 1 && *(volatile uint32_t*)&pend[r - 1] == 0) return;
+  uint64_t piece_base = 0;
+  if constexpr (LVL) piece_base = jframes[jf0].piece0;
   // ZD_J_XREG regions over the chip, each swept by the workgroups of 8 / XREG
   // XCDs (workgroup b runs on XCD b mod 8)
   constexpr uint32_t XR = ZD_J_XREG, XG = 8 / ZD_J_XREG;
@@ -5696,6 +5727,7 @@ __global__ __launch_bounds__(256) void zd_k_jround(uint8_t* outbase, const Frame
       const uint64_t i = i0 + 16 * k + row;           // a wave's rows: four consecutive pieces per k
       pc[k] = x * R + rb + i;
       act[k] = i < Rs && rb + i < R && pc[k] < n_pieces;
+      if constexpr (LVL) pc[k] += piece_base;
     }
     JFrame JF[JW_K];
     uint8_t dn[JW_K];
@@ -6038,6 +6070,12 @@ __global__ __launch_bounds__(256) void zd_k_compact(const uint8_t* __restrict__ 
 // ---------------------------------------------------------------------------
 // launch
 // ---------------------------------------------------------------------------
+// zd_k_jround's grid over `pieces` pieces: a multiple of 8 (one eighth per XCD)
+static dim3 j_grid(uint64_t pieces, uint32_t cus) {
+  const uint64_t gw = (pieces + 16 * JW_K - 1) / (16 * JW_K);   // pieces per workgroup sweep
+  const uint64_t gmax = 8ull * cus;                              // what fits at once: 8 workgroups per CU
+  return dim3((uint32_t)(gw < gmax ? (gw + 7) & ~7ull : (gmax + 7) & ~7ull));
+}
 hipError_t launch_pipeline(const LaunchArgs& a) {
   uint8_t* ws = a.ws;
   const Workspace& W = a.W;
@@ -6173,13 +6211,49 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
       // frames find their parents complete.  Levels past the first launch even
       // when K0 copies every frame whole: the workgroups check their parents.
       if (n && k4_work) if ((e = dom(DOM_K4, 0)) != hipSuccess) return e;
+      // ZD_F_CHAIN_BLOCK_PARALLEL: K4J's tables once over every J frame (none of
+      // them reads a prefix), then per level, behind the level's streaming
+      // frames, the scatter over the level's segments and the rounds over the
+      // level's pieces (LaunchArgs::chain_j).  A level's frames find every
+      // frame of the levels below final, streaming or J: a J frame's bytes are
+      // final once its level's last zd_k_jround has emitted them.
+      const bool cj = a.chain_j && a.n_jframes;
+      auto* jframes = (const JFrame*)(ws + W.jframes);
+      auto* jd = (const JBlkDesc*)(ws + W.jblkd);
+      auto* jb = (JBlk*)(ws + W.jblk);
+      auto* jseg = (JSeg*)(ws + W.jseg);
+      auto* jsd = (const JSegDesc*)(ws + W.jsegd);
+      if (cj) {
+        hipLaunchKernelGGL(zd_k_jsum, dim3(a.n_jseg), dim3(64), 0, st, a.src, (const FrameState*)fstate, blocks, comp,
+                           (const CompState*)cstate, (const uint64_t*)seqs, (const uint16_t*)fses, jframes, jd, jsd,
+                           jseg);
+        hipLaunchKernelGGL(zd_k_jsum_blocks, dim3((a.n_jblk + 63) / 64), dim3(64), 0, st, (const FrameState*)fstate,
+                           blocks, comp, (const CompState*)cstate, jframes, jd, a.n_jblk, jb, jseg);
+        hipLaunchKernelGGL(zd_k_jprefix, dim3(a.n_jframes), dim3(64 * JP_WAVES), 0, st, frames, fstate, jframes, jd, jb);
+      }
       uint32_t begin = 0;
-      for (uint32_t l = 0; l < a.chain_levels; begin += a.chain_count[l], l++)
+      for (uint32_t l = 0; l < a.chain_levels; begin += a.chain_count[l], l++) {
         if (a.chain_count[l] && (l || k4_work))
           hipLaunchKernelGGL(zd_k_execute_chain, dim3(a.chain_count[l]), dim3(64), 0, st, a.src, a.out, frames, fstate,
                              blocks, comp, (const CompState*)cstate, (const uint8_t*)(ws + W.lits),
                              (const uint64_t*)seqs, (const uint16_t*)fses, a.chain_order, begin, a.chain_parent,
                              (const uint8_t* const*)(ws + W.dict_ptrs));
+        if (!cj || !a.chain_j[l].njf) continue;
+        const JLevel& L = a.chain_j[l];
+        hipLaunchKernelGGL((zd_k_jscatter<true, true>), dim3((uint32_t)L.nseg), dim3(64), 0, st, a.src, fstate, blocks,
+                           comp, (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
+                           (const uint16_t*)fses, jframes, jd, (const JBlk*)jb, (const JSeg*)jseg, jsd,
+                           (uint32_t*)(ws + W.jst), frames, (const uint8_t* const*)(ws + W.dict_ptrs),
+                           (uint32_t)L.seg0, a.chain_parent);
+        // the level's own pend slots (3 a level: rounds 1 and 2 use [1] and [2])
+        uint32_t* pend = (uint32_t*)(ws + W.jpend) + 3 * l;
+        const dim3 gr = j_grid(L.npieces, a.cus);
+        const uint32_t nr = a.j_rounds < 2 ? a.j_rounds : 2u;
+        for (uint32_t r = 1; r <= nr && L.npieces; r++)
+          hipLaunchKernelGGL(zd_k_jround<true>, gr, dim3(256), 0, st, a.out, frames, fstate, jframes, a.n_jframes,
+                             (uint32_t)L.jf0, L.npieces, (uint32_t*)(ws + W.jst), pend, ws + W.jdone, r > 1 ? R.j_hops2 : R.j_hops, r,
+                             (uint32_t)(r == nr), r == nr ? a.j_rounds - nr + 1 : 1u);
+      }
       if (n && k4_work) if ((e = dom(DOM_K4, 1)) != hipSuccess) return e;
       return hipSuccess;
     }
@@ -6246,7 +6320,7 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     if ((e = k4f((const uint32_t*)(ws + W.list_k4f), a.n_k4f, s)) != hipSuccess) return e;
   }
   if ((e = ev(5)) != hipSuccess) return e;
-  if (a.n_jframes) {
+  if (a.n_jframes && !(R.k4 == K4_CHAIN && a.chain_j)) {   // (a flagged chain batch: level by level, in k4 above)
     auto* jframes = (const JFrame*)(ws + W.jframes);
     auto* jd = (const JBlkDesc*)(ws + W.jblkd);
     auto* jb = (JBlk*)(ws + W.jblk);
@@ -6264,21 +6338,19 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
       hipLaunchKernelGGL(zd_k_jscatter<true>, dim3(a.n_jseg), dim3(64), 0, s, a.src, fstate, blocks, comp,
                          (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
                          (const uint16_t*)fses, jframes, jd, (const JBlk*)jb, (const JSeg*)jseg, jsd, jst, frames,
-                         (const uint8_t* const*)(ws + W.dict_ptrs));
+                         (const uint8_t* const*)(ws + W.dict_ptrs), 0u, (const int32_t*)nullptr);
     else
       hipLaunchKernelGGL(zd_k_jscatter<false>, dim3(a.n_jseg), dim3(64), 0, s, a.src, fstate, blocks, comp,
                          (const CompState*)cstate, (const uint8_t*)(ws + W.lits), (const uint64_t*)seqs,
                          (const uint16_t*)fses, jframes, jd, (const JBlk*)jb, (const JSeg*)jseg, jsd, jst,
-                         (const FrameDesc*)nullptr, (const uint8_t* const*)nullptr);
-    const uint64_t gw = (a.j_pieces + 16 * JW_K - 1) / (16 * JW_K);   // pieces per workgroup sweep
-    const uint64_t gmax = 8ull * a.cus;                              // what fits at once: 8 workgroups per CU
-    const dim3 gr((uint32_t)(gw < gmax ? (gw + 7) & ~7ull : (gmax + 7) & ~7ull));   // a multiple of 8 (one eighth per XCD)
+                         (const FrameDesc*)nullptr, (const uint8_t* const*)nullptr, 0u, (const int32_t*)nullptr);
+    const dim3 gr = j_grid(a.j_pieces, a.cus);
     // round 1 one launch, the rest as one launch of sweeps
     // (one launch of all the sweeps: 1.43 ms for the rounds of c3s, against
     // 1.38 with the first round launched alone; three launches, 1.38 too)
     const uint32_t nr = a.j_rounds < 2 ? a.j_rounds : 2u;
     for (uint32_t r = 1; r <= nr; r++)
-      hipLaunchKernelGGL(zd_k_jround, gr, dim3(256), 0, s, a.out, frames, fstate, jframes, a.n_jframes,
+      hipLaunchKernelGGL(zd_k_jround<false>, gr, dim3(256), 0, s, a.out, frames, fstate, jframes, a.n_jframes, 0u,
                          a.j_pieces, jst, pend, ws + W.jdone, r > 1 ? R.j_hops2 : R.j_hops, r, (uint32_t)(r == nr),
                          r == nr ? a.j_rounds - nr + 1 : 1u);
     if ((e = dom(DOM_K4J, 1)) != hipSuccess) return e;
@@ -6344,9 +6416,9 @@ __global__ __launch_bounds__(256) void zd_k_reset_dict(uint8_t* ws, Workspace W,
   reset_body(ws, W, fs_words, cs_words, jp_words, jdone_bytes, cs_keep);
 }
 hipError_t launch_reset(uint8_t* ws, const Workspace& W, uint64_t n_frames, uint64_t n_comps, bool k4j,
-                        uint64_t j_pieces, hipStream_t s, uint32_t keep_comps) {
+                        uint64_t j_pieces, hipStream_t s, uint32_t keep_comps, uint32_t jpend_words) {
   const uint64_t fs_words = n_frames * sizeof(FrameState) / 4, cs_words = std::max<uint64_t>(n_comps, 1) * sizeof(CompState) / 4;
-  const uint32_t jp_words = k4j ? (uint32_t)(J_MAX_ROUNDS + 1) : 0u;
+  const uint32_t jp_words = k4j ? jpend_words : 0u;
   const uint64_t jdone = k4j ? std::max<uint64_t>(j_pieces, 1) : 0;
   const uint64_t work = std::max(std::max(fs_words, cs_words), jdone / 16 + 16);
   const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, (work + 1023) / 1024);
@@ -6622,11 +6694,58 @@ hipError_t launch_plan_shape(const HostFrame* frames, uint64_t nf, uint32_t k4j_
   if (nf) hipLaunchKernelGGL(zd_k_plan_shape, dim3((uint32_t)((nf + 255) / 256)), dim3(256), 0, s, frames, nf, k4j_min, out);
   return hipGetLastError();
 }
+// The K4J counts of frame order[q] into column w at col[w * nf + q] (before
+// the count pass's scan turns the counts into starts)
+__global__ __launch_bounds__(256) void zd_k_plan_jgather(const PlanCounts* __restrict__ cnt,
+                                                         const uint32_t* __restrict__ order, uint64_t nf,
+                                                         uint64_t* col) {
+  const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= nf) return;
+  const uint32_t f = order[q];
+  if (f >= nf) return;                         // (never: order[] is a permutation of the frames)
+  uint64_t J[PLAN_J_COLS];
+  plan_j_get(cnt[f], J);
+  for (int w = 0; w < PLAN_J_COLS; w++) col[(uint64_t)w * nf + q] = J[w];
+}
+// The scanned columns back to the frames (j_at), and the levels' first entries
+// (lev: 3 words a level; level l's frames are order[cursor[l] - count[l] ...])
+__global__ __launch_bounds__(256) void zd_k_plan_jplace(const uint64_t* __restrict__ col,
+                                                        const uint32_t* __restrict__ order,
+                                                        const uint32_t* __restrict__ lcount, uint64_t nf,
+                                                        uint64_t* j_at, uint64_t* lev) {
+  const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (blockIdx.x == 0) {
+    const uint32_t l = threadIdx.x, c = lcount[l], end = lcount[CHAIN_LEVELS + l];
+    static_assert(CHAIN_LEVELS == 256, "zd_k_plan_jplace: one level a thread");
+    if (c && end >= c && (uint64_t)(end - c) < nf) {
+      const uint64_t b = end - c;
+      lev[3 * l + 0] = col[(uint64_t)PJ_FRAMES * nf + b];
+      lev[3 * l + 1] = col[(uint64_t)PJ_SEG * nf + b];
+      lev[3 * l + 2] = col[(uint64_t)PJ_PIECES * nf + b];
+    }
+  }
+  if (q >= nf) return;
+  const uint32_t f = order[q];
+  if (f >= nf) return;
+  for (int w = 0; w < PLAN_J_COLS; w++) j_at[(uint64_t)PLAN_J_COLS * f + w] = col[(uint64_t)w * nf + q];
+}
 hipError_t launch_plan_count(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
                              uint64_t* cnt, uint64_t* tot, PlanShape* shape, hipStream_t s, uint32_t dict_comps) {
+  return launch_plan_count(X, frames, blocks, nf, cnt, tot, shape, s, dict_comps, nullptr);
+}
+hipError_t launch_plan_count(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
+                             uint64_t* cnt, uint64_t* tot, PlanShape* shape, hipStream_t s, uint32_t dict_comps,
+                             const PlanJOrder* jo) {
   const uint32_t nt = (uint32_t)((nf + 255) / 256);
   if (nf) {
     hipLaunchKernelGGL(zd_k_plan_count, dim3(nt), dim3(256), 0, s, X, frames, blocks, nf, (PlanCounts*)cnt, shape);
+    if (jo) {
+      hipLaunchKernelGGL(zd_k_plan_jgather, dim3(nt), dim3(256), 0, s, (const PlanCounts*)cnt, jo->order, nf, jo->col);
+      hipError_t e = launch_scan64(jo->col, nullptr, nf, PLAN_J_COLS, nf, jo->scratch, s);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(zd_k_plan_jplace, dim3(nt), dim3(256), 0, s, (const uint64_t*)jo->col, jo->order, jo->lcount,
+                         nf, jo->j_at, jo->lev);
+    }
     hipLaunchKernelGGL(zd_k_plan_scan_tiles, dim3(nt), dim3(256), 0, s, cnt, nf, tot);
   }
   hipLaunchKernelGGL(zd_k_plan_scan_sums, dim3(1), dim3(64), 0, s, tot, (uint64_t)nt, (uint64_t)dict_comps);

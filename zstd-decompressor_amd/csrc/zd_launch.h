@@ -46,7 +46,15 @@ struct LaunchArgs {
   const int32_t* chain_parent = nullptr;
   const uint32_t* chain_count = nullptr;
   uint32_t chain_levels = 0;
+  // a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL (null otherwise): level
+  // l's J frames, scatter segments and pieces (host, chain_levels entries), one
+  // contiguous range each (zd_plan.h plan_j_order); W.jpend then holds
+  // jpend_chain_words(chain_levels) words, three a level
+  const JLevel* chain_j = nullptr;
 };
+// W.jpend's u32 words: a pointer-jumping counter per round, or three per level of a flagged chain plan
+constexpr uint32_t JPEND_WORDS = (uint32_t)(J_MAX_ROUNDS + 1);
+inline uint32_t jpend_chain_words(uint32_t levels) { return 3 * (levels ? levels : 1u); }
 
 // K1 table parse/build -> K2 Huffman literals -> K3 FSE sequences -> K4 execute.
 hipError_t launch_pipeline(const LaunchArgs& a);
@@ -54,7 +62,8 @@ hipError_t launch_pipeline(const LaunchArgs& a);
 // zd_decode_async's state reset (frame / block states, K1 and K4J counters, K4J done flags).
 // keep_comps: the leading block states left as they are (a dictionary plan's prebuilt comps)
 hipError_t launch_reset(uint8_t* ws, const Workspace& W, uint64_t n_frames, uint64_t n_comps, bool k4j,
-                        uint64_t j_pieces, hipStream_t s, uint32_t keep_comps = 0);
+                        uint64_t j_pieces, hipStream_t s, uint32_t keep_comps = 0,
+                        uint32_t jpend_words = (uint32_t)(J_MAX_ROUNDS + 1));
 
 // zd_k_dict_tables' result (zd_dict_create reads it once)
 struct DictTables {
@@ -105,6 +114,23 @@ hipError_t launch_plan_count(const PlanCtx& X, const HostFrame* frames, const Ho
                              uint64_t* cnt, uint64_t* tot, PlanShape* shape, hipStream_t s, uint32_t dict_comps = 0);
 hipError_t launch_plan_fill(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
                             const uint64_t* cnt, const uint64_t* tot, const Sink& S, hipStream_t s);
+// The level-major K4J numbering of a chain batch created with
+// ZD_F_CHAIN_BLOCK_PARALLEL (zd_plan.h plan_j_order, on the device), between
+// the count pass and its scan: launch_plan_count's `jo` gathers the frames' K4J
+// counts in order[] order into PLAN_J_COLS columns of nf words (col), scans
+// them (zd_k_scan_*; scratch: PLAN_J_COLS x (tiles + 1) words), writes every
+// frame's starts to j_at (PLAN_J_COLS words a frame: PlanCtx::j_at of the fill
+// pass) and the levels' first J frame, segment and piece to lev (3 words a
+// level, for the levels lcount -- BatchCarve::lcount after zd_k_chain_bucket --
+// gives a frame).
+struct PlanJOrder {
+  const uint32_t* order;     // device: the frames grouped by level
+  const uint32_t* lcount;    // device: counts | cursors (the levels' ends)
+  uint64_t *col, *scratch, *j_at, *lev;
+};
+hipError_t launch_plan_count(const PlanCtx& X, const HostFrame* frames, const HostBlock* blocks, uint64_t nf,
+                             uint64_t* cnt, uint64_t* tot, PlanShape* shape, hipStream_t s, uint32_t dict_comps,
+                             const PlanJOrder* jo);
 
 // A batch's chunks (zd_batch_create), device arrays of n entries: where chunk
 // i lies (src, size) and where its copy sits in the gathered buffer (off, a

@@ -110,9 +110,64 @@ struct PlanCtx {
   // size, the first repeat offsets are 1, 4, 8, there are no previous tables,
   // and a frame that names a Dictionary_ID is ZD_E_DICT_MISMATCH.  With
   // k4j_mode 1 (a batch created with ZD_F_BLOCK_PARALLEL, no chain: zd_route.h
-  // k4j_mode_behind) every such frame with a compressed block goes to K4J.
+  // k4j_mode_behind; a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL:
+  // k4j_mode_plan, with j_at below) every such frame with a compressed block
+  // goes to K4J.
   const uint64_t* prefix_bytes;
+  // Optional K4J numbering (a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL;
+  // null everywhere else): frame fi's K4J entries start at j_at[PLAN_J_COLS * fi
+  // ...] -- its JFrame, first J block, first segment, first state word, first
+  // piece (PlanJ order) -- instead of at the running counts, so that the J
+  // frames are numbered level-major (plan_j_order) and every level of the chain
+  // owns one contiguous range of each.  The running counts advance as ever
+  // (the totals, and the per-frame counts that plan_j_order scans).
+  const uint64_t* j_at;
 };
+
+// The K4J columns of PlanCounts, in j_at's order
+constexpr int PLAN_J_COLS = 5;
+enum PlanJ : int { PJ_FRAMES = 0, PJ_BLK = 1, PJ_SEG = 2, PJ_WORDS = 3, PJ_PIECES = 4 };
+
+ZD_HD inline void plan_j_get(const PlanCounts& c, uint64_t j[PLAN_J_COLS]) {
+  j[PJ_FRAMES] = c.jframes; j[PJ_BLK] = c.jblk; j[PJ_SEG] = c.jseg; j[PJ_WORDS] = c.jwords; j[PJ_PIECES] = c.jpieces;
+}
+// One level's share of K4J's grids in a flagged chain plan: its J frames,
+// scatter segments and 16-byte pieces, each one contiguous range
+struct JLevel { uint64_t jf0, njf, seg0, nseg, piece0, npieces; };
+// Level-major K4J numbering: jcnt holds each frame's own K4J counts
+// (PLAN_J_COLS words a frame, plan_frame's count pass), order[] the frames
+// grouped by level with the levels ascending (count[l] frames of level l).
+// j_at gets each frame's starts -- an exclusive scan of the counts in order[]
+// order, which is what the device planner does with zd_k_scan_* over the
+// gathered columns -- and lev[l] level l's ranges.  Returns the totals in tot.
+inline void plan_j_order(const uint64_t* jcnt, const uint32_t* order, const uint32_t* count, uint32_t levels,
+                         uint64_t* j_at, JLevel* lev, uint64_t tot[PLAN_J_COLS]) {
+  uint64_t run[PLAN_J_COLS] = {0, 0, 0, 0, 0};
+  uint64_t q = 0;
+  for (uint32_t l = 0; l < levels; l++) {
+    JLevel L{run[PJ_FRAMES], 0, run[PJ_SEG], 0, run[PJ_PIECES], 0};
+    for (uint32_t k = 0; k < count[l]; k++, q++) {
+      const uint64_t f = order[q];
+      for (int w = 0; w < PLAN_J_COLS; w++) { j_at[PLAN_J_COLS * f + w] = run[w]; run[w] += jcnt[PLAN_J_COLS * f + w]; }
+    }
+    L.njf = run[PJ_FRAMES] - L.jf0; L.nseg = run[PJ_SEG] - L.seg0; L.npieces = run[PJ_PIECES] - L.piece0;
+    lev[l] = L;
+  }
+  for (int w = 0; w < PLAN_J_COLS; w++) tot[w] = run[w];
+}
+// The levels' ranges from their first entries (the device planner reads back
+// start[3 * l + {0, 1, 2}] = level l's first J frame, segment and piece, set for
+// the levels that have a frame) and the plan's totals
+inline void plan_j_levels(const uint64_t* start, const uint32_t* count, uint32_t levels, uint64_t jframes,
+                          uint64_t jseg, uint64_t jpieces, JLevel* lev) {
+  uint64_t end[3] = {jframes, jseg, jpieces};
+  for (uint32_t l = levels; l-- > 0;) {
+    if (!count[l]) { lev[l] = JLevel{end[0], 0, end[1], 0, end[2], 0}; continue; }
+    const uint64_t* s = start + 3 * (uint64_t)l;
+    lev[l] = JLevel{s[0], end[0] - s[0], s[1], end[1] - s[1], s[2], end[2] - s[2]};
+    end[0] = s[0]; end[1] = s[1]; end[2] = s[2];
+  }
+}
 
 // The entry of Dictionary_ID id (non-zero) in a table sorted by ID, or -1.
 ZD_HD inline int32_t plan_dict_find(const PlanDict* t, uint32_t n, uint64_t id) {
@@ -338,8 +393,12 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
     fs.key = plan_min(fs.key, make_key(PH_LIMIT, 0, 0, 0, ZD_E_OUT_OF_DOMAIN));
   if (to_j) {
     fd.lds = 2;
+    // the frame's K4J indices: the running ones, or its level-major places
+    uint64_t J[PLAN_J_COLS];
+    plan_j_get(c, J);
+    if (X.j_at) for (int w = 0; w < PLAN_J_COLS; w++) J[w] = X.j_at[PLAN_J_COLS * (uint64_t)fi + w];
     uint64_t nseq = 0;
-    uint32_t njs = (uint32_t)c.jseg;
+    uint32_t njs = (uint32_t)J[PJ_SEG];
     for (uint32_t k = 0; k < fd.nblocks; k++) {
       const HostBlock& hb = hblocks[hf.b0 + k];
       const uint32_t bn = hb.type == 2 ? hb.cb.nseq : 0u;
@@ -347,22 +406,22 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
       if (FILL) {
         JBlkDesc d{};
         d.block = fd.first_block + k;
-        d.jframe = (uint32_t)c.jframes;
+        d.jframe = (uint32_t)J[PJ_FRAMES];
         d.j = k;
         d.seg0 = njs;
-        for (uint32_t g = 0; g == 0 || g * J_SEG < bn; g++) S.jsegd[njs++] = JSegDesc{(uint32_t)c.jblk + k, g};
-        S.jblkd[c.jblk + k] = d;
+        for (uint32_t g = 0; g == 0 || g * J_SEG < bn; g++) S.jsegd[njs++] = JSegDesc{(uint32_t)J[PJ_BLK] + k, g};
+        S.jblkd[J[PJ_BLK] + k] = d;
       }
     }
     if (FILL) {
       JFrame jf{};
-      jf.base = c.jwords;                      // word index: frame pieces of 16 words are 64-byte lines
+      jf.base = J[PJ_WORDS];                   // word index: frame pieces of 16 words are 64-byte lines
       jf.cap = cap;
-      jf.piece0 = c.jpieces;
+      jf.piece0 = J[PJ_PIECES];
       jf.frame = fi;
-      jf.jb0 = (uint32_t)c.jblk;
+      jf.jb0 = (uint32_t)J[PJ_BLK];
       jf.njb = fd.nblocks;
-      S.jframes[c.jframes] = jf;
+      S.jframes[J[PJ_FRAMES]] = jf;
     }
     if (jm) jm->note(nseq);
     c.jframes++;

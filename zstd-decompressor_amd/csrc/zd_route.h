@@ -97,6 +97,13 @@ inline int k4j_mode_of(uint32_t flags, const RouteEnv& E) {
 inline int k4j_mode_behind(int mode, uint32_t flags, bool dict, bool prefix, bool chain) {
   return !dict ? mode : (prefix && !chain && (flags & ZD_F_BLOCK_PARALLEL) && mode == 1) ? 1 : 0;
 }
+// A chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL: K4J for every frame
+// with a compressed block, level by level (the flag means nothing anywhere else)
+inline bool chain_j(uint32_t flags, bool chain) { return chain && (flags & ZD_F_CHAIN_BLOCK_PARALLEL) != 0; }
+// The mode of any plan: k4j_mode_behind, with the chain case beside it
+inline int k4j_mode_plan(int mode, uint32_t flags, bool dict, bool prefix, bool chain) {
+  return chain_j(flags, chain) ? 1 : k4j_mode_behind(mode, flags, dict, prefix, chain);
+}
 
 // What a plan is built for (plan_ctx).  `in` as route_plan's, its `context` set
 // for a dictionary or dictionary-set plan too (`dict`): the streaming executor only.

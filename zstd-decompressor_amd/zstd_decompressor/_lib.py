@@ -272,6 +272,7 @@ F_SEQ_NO_LATENCY = 256 # K3Q instead of the one-block-per-wave K3L in plans of f
 F_K1_SPLIT = 512       # K1 as a parse pass and a build pass in a plan of any size
 F_VERIFY_CHECKSUM = 1024  # Content_Checksums verified inside the decode launch (zd_k_verify): CHECKSUM_WRONG
 F_LONG_WINDOW = 2048   # accept a Window_Size up to 2 GiB (default: the reference's 8 MiB limit)
+F_CHAIN_BLOCK_PARALLEL = 4096  # a chain batch (parents=): frames with a compressed block -> K4J, level by level
 SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
 SIZES_LONG_WINDOW = 2048  # zd_chunk_sizes_device: the chunks will be decoded with F_LONG_WINDOW (the same bit)
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)
