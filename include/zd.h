@@ -156,9 +156,10 @@ typedef struct zd_plan zd_plan;
  * dictionary or a dictionary set, chain batches and zd_context ignore both
  * flags (the streaming executor only; a chain batch has a flag of its own,
  * ZD_F_CHAIN_BLOCK_PARALLEL); a prefix batch (zd_batch_create_prefix,
- * zd_batch_create_device_prefix) ignores the automatic rule and takes K4J only
- * when ZD_F_BLOCK_PARALLEL asks for it: large deltas, whose hundreds of blocks
- * one wave would decode one after another. */
+ * zd_batch_create_device_prefix) ignores the plain plans' automatic rule and
+ * takes K4J when ZD_F_BLOCK_PARALLEL asks for it -- large deltas, whose
+ * hundreds of blocks one wave would decode one after another -- or chunk by
+ * chunk by the batches' own rule, ZD_F_AUTO_EXECUTOR. */
 #define ZD_F_BLOCK_PARALLEL 2u  /* every frame with a compressed block -> K4J (block-parallel execute);
                                    prefix batches included */
 #define ZD_F_FRAME_SERIAL   4u  /* no frame -> K4J (the streaming per-frame executor) */
@@ -241,8 +242,48 @@ typedef struct zd_plan zd_plan;
  * ZD_F_FRAME_SERIAL.  Everywhere else the flag is accepted and ignored: plain,
  * dictionary and prefix batches, zd_plan_*, zd_decompress*, the sharded calls.
  * K4J is several times slower than the streaming executor on small frames
- * (16 KiB pages; README), which is why no rule sets this flag by itself. */
+ * (16 KiB pages; README), so this flag forces the choice for the whole batch;
+ * ZD_F_AUTO_EXECUTOR below chooses chunk by chunk. */
 #define ZD_F_CHAIN_BLOCK_PARALLEL 4096u
+/* Prefix and chain batches: each chunk's executor chosen by rule (opt-in).  In a
+ * prefix batch (zd_batch_create_prefix, zd_batch_create_device_prefix) and in a
+ * chain batch (zd_batch_create_chain, zd_batch_create_device_chain) a chunk's
+ * frame executes on K4J when it could under the forcing flag -- a zstd frame
+ * that did not fail to index, with a compressed block, a capacity within K4J's
+ * 32 GiB and a prefix of at most 0x7FFF0000 bytes -- and one of these holds:
+ *  (a) it has at least ZD_AUTO_MIN_BLOCKS compressed blocks -- at least
+ *      ZD_AUTO_MIN_BLOCKS_FEW when the batch's width is at most
+ *      ZD_AUTO_FEW_CHUNKS -- and the batch has at most ZD_AUTO_MAX_CANDIDATES
+ *      such frames.  The width is the number of chunks that execute together:
+ *      a prefix batch's chunk count, a chain batch's widest level;
+ *  (b) the streaming executor cannot hold it: prefix size plus capacity pass
+ *      0x7FFF0000 while the prefix alone fits.  Without a forcing flag such a
+ *      chunk is ZD_E_OUT_OF_DOMAIN; with this flag it decodes.
+ * Every other frame takes the batch's streaming executor.  A chain batch with
+ * the flag is laid out and launched like one created with
+ * ZD_F_CHAIN_BLOCK_PARALLEL (level by level; a level without a K4J frame queues
+ * no K4J launch).  zd_batch_info.executors carries ZD_EXEC_K4J only when some
+ * frame went there, and zd_batch_info2.k4j_chunks counts them.  The forcing
+ * flags win: in a prefix batch ZD_F_BLOCK_PARALLEL and ZD_F_FRAME_SERIAL behave
+ * as without this flag, in a chain batch ZD_F_CHAIN_BLOCK_PARALLEL does (the
+ * other two stay ignored there).  A chunk whose pointer jumping does not
+ * converge is decoded again inside zd_batch_results, as with the forcing flags.
+ * The same bytes, statuses and lengths as without the flag, but for (b).
+ * Everywhere else the flag is accepted and ignored: plain, dictionary and
+ * dictionary-set batches, zd_plan_*, zd_decompress*, the sharded calls.  Without
+ * the flag nothing changes.
+ * The four constants (measured on prefix and chain batches of text deltas,
+ * scripts/time_auto_exec.py, EXPERIMENTS.md): */
+#define ZD_F_AUTO_EXECUTOR 8192u
+#define ZD_AUTO_MIN_BLOCKS      4    /* (a): compressed blocks a frame needs for K4J (256 deltas of 4 blocks: K4J
+                                        2.3 ms against 2.6 streaming; of 2 blocks: 1.44 against 1.44) */
+#define ZD_AUTO_MIN_BLOCKS_FEW  2    /*      ... at a width of at most ZD_AUTO_FEW_CHUNKS (64 deltas of 2 blocks:
+                                        0.80 ms against 1.36; of 1 block: 0.73 against 0.75) */
+#define ZD_AUTO_FEW_CHUNKS      64
+#define ZD_AUTO_MAX_CANDIDATES  256  /* (a) holds only while at most this many frames of the batch meet it (K4J's
+                                        time grows with the frames it takes, the streaming executor's with the
+                                        longest frame: 256 deltas of 16 blocks 8.2 ms against 10.4, 1,024 of them
+                                        33.1 against 11.4; the plain plans' rule has 16 and 1,024 here) */
 
 /* zd_plan_info.executors: */
 #define ZD_EXEC_FUSED 1u   /* zd_k_fused: tables, FSE chains and execution per group of four
@@ -542,6 +583,12 @@ typedef struct zd_batch_info {
   uint64_t prefix_bytes_total; /* a prefix batch: the sum of prefix_bytes[i] over the chunks that
                                 * kept their prefix (0 for any other batch) */
 } zd_batch_info;
+/* zd_batch_info with what came after prefix_bytes_total (zd_batch_info_get_sized
+ * writes it when info_bytes covers it: pass &x.info and sizeof x). */
+typedef struct zd_batch_info2 {
+  zd_batch_info info;
+  uint64_t k4j_chunks;      /* chunks whose frame executes on K4J (any batch kind; 0 without ZD_EXEC_K4J) */
+} zd_batch_info2;
 
 /* A batch over nchunks chunks: chunk i is the src_bytes[i] bytes at device
  * address d_src[i] and decodes into [d_dst[i], d_dst[i] + dst_cap[i]).  The
@@ -685,8 +732,8 @@ int  zd_batch_create_device_dicts(const void* const* d_src_ptrs, const uint64_t*
  * a destination range.  nchunks == 0 is ZD_OK.
  * Limits (not in this interface): no packed prefix batches; prefixes cannot be
  * re-pointed after creation; no prefixes on the LDS-resident or fused
- * executors, and on the block-parallel one only by ZD_F_BLOCK_PARALLEL (no
- * automatic rule yet); none in zd_plan_*, the sharded calls or zd_context;
+ * executors, and on the block-parallel one by ZD_F_BLOCK_PARALLEL or, chunk by
+ * chunk, by ZD_F_AUTO_EXECUTOR; none in zd_plan_*, the sharded calls or zd_context;
  * no window past 2 GiB.  (A
  * chunk whose prefix is another chunk's output of the same launch: a chain
  * batch, zd_batch_create_chain.) */
@@ -758,8 +805,12 @@ int  zd_batch_create_device_prefix(const void* const* d_src_ptrs, const uint64_t
  *    ZD_E_NOT_DECODED until zd_batch_results, which decodes that chunk and every
  *    chunk behind it again on the streaming executor (one internal chain batch)
  *    and updates the device arrays.
+ *  - ZD_F_AUTO_EXECUTOR: the same layout and launches, with each chunk's frame
+ *    routed by the rule at the flag (the width is the widest level's chunk
+ *    count); page links stay on zd_k_execute_chain, large links go to K4J, and a
+ *    failure crosses the executors as it crosses levels.
  * Everything else is a prefix batch's: the streaming executor only (but for
- * ZD_F_CHAIN_BLOCK_PARALLEL; ZD_F_BLOCK_PARALLEL is ignored), no
+ * ZD_F_CHAIN_BLOCK_PARALLEL and ZD_F_AUTO_EXECUTOR; ZD_F_BLOCK_PARALLEL is ignored), no
  * dictionary or set, not packed, ZD_F_SKIPPABLE refused, the sources gathered
  * at creation, zd_batch_decode_async free of allocation and host
  * synchronisation, capturable and re-launchable; every zd_batch_* call works on
@@ -896,7 +947,9 @@ int  zd_batch_bind_output(zd_batch* batch, void* d_out, uint64_t cap);
  * passes no more -- and zd_batch_info_get_sized writes the first info_bytes
  * bytes of the current struct (at most all of it; fewer than 80 is
  * ZD_E_INVALID_ARG).  C and C++ code that includes this header gets the sized
- * call under the old name, so its whole struct is filled. */
+ * call under the old name, so its whole struct is filled.  What came later
+ * (zd_batch_info2: k4j_chunks at byte 88) follows the struct in the same
+ * call: zd_batch_info_get_sized(b, &x.info, sizeof x) with a zd_batch_info2 x. */
 int  zd_batch_info_get(const zd_batch* batch, zd_batch_info* info);
 int  zd_batch_info_get_sized(const zd_batch* batch, zd_batch_info* info, size_t info_bytes);
 #ifndef ZD_NO_SIZED_INFO_MACRO

@@ -154,7 +154,9 @@ struct zd_plan {
   const uint32_t* d_chain_order = nullptr;
   const int32_t* d_chain_parent = nullptr;
   std::vector<uint32_t> chain_count;
-  // a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL (zd_route.h chain_j):
+  // a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL, or routed frame by
+  // frame under ZD_F_AUTO_EXECUTOR (zd_route.h chain_j_layout; there any level,
+  // or every level, may be without a J frame):
   // its J frames are numbered level-major (zd_plan.h plan_j_order), chain_j[l]
   // level l's ranges of K4J's grids.  What the planners need for that: the
   // frames by level on the host (host arrays), or the batch's level counters on
@@ -162,7 +164,15 @@ struct zd_plan {
   std::vector<JLevel> chain_j;
   std::vector<uint32_t> h_chain_order;
   const uint32_t* d_chain_lcount = nullptr;
-  bool chain_on_j() const { return zd::chain_j(flags, chain); }
+  bool chain_on_j() const { return zd::chain_j_layout(flags, chain); }
+  // the width ZD_F_AUTO_EXECUTOR's rule reads (the chunks that execute together)
+  // and the block minimum of the plan's rule (zd_plan.h plan_k4j_min)
+  uint64_t auto_width() const {
+    uint64_t w = nframes;
+    if (chain) { w = 0; for (uint32_t c : chain_count) w = std::max<uint64_t>(w, c); }
+    return w;
+  }
+  uint32_t k4j_min() const { return plan_k4j_min(flags, prefix, chain, nframes, auto_width()); }
   uint32_t jpend_words() const {
     return chain_on_j() ? jpend_chain_words((uint32_t)chain_count.size()) : JPEND_WORDS;
   }
@@ -392,7 +402,8 @@ bool host_single_block_frames(const zd_plan* P) {
 // The per-frame pass's plan-wide inputs (routing included): `single` =
 // every frame a single-block zstd frame, `j_candidates` = frames K4J would
 // take in automatic mode (frames without a walk-found error and with at
-// least k4j_min compressed blocks; counted only when the mode is automatic).
+// least k4j_min compressed blocks; counted only when the mode is automatic,
+// or for ZD_F_AUTO_EXECUTOR's rule).
 PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t out_len0,
                  const uint64_t rep0[3], uint64_t fixed_cap, bool single, uint64_t j_candidates) {
   PlanCtx X{};
@@ -429,13 +440,8 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   const PlanRoute r = plan_route(in, X.dict, route_env());
   X.fused = r.fused;
   X.k4f_on = r.k4f;
-  X.k4j_mode = k4j_mode_of(P->flags, route_env());
-  X.k4j_min = P->nframes <= K4J_FEW_FRAMES ? K4J_MIN_BLOCKS_FEW : K4J_MIN_BLOCKS;
-  X.k4j_auto = X.k4j_mode < 0 && out_len0 == 0 && j_candidates > 0 && j_candidates <= K4J_MAX_FRAMES;
-  if (X.dict) {
-    X.k4j_auto = false;
-    X.k4j_mode = k4j_mode_plan(X.k4j_mode, P->flags, true, P->prefix, P->chain);
-  }
+  plan_k4j_fields(X, P->flags, route_env(), X.dict, P->prefix, P->chain, out_len0, P->nframes, P->auto_width(),
+                  j_candidates);
   return X;
 }
 
@@ -592,8 +598,8 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
                const uint64_t rep0[3], uint64_t fixed_cap, bool staged = false) {
   P->cus = device_cus();
   uint64_t j_candidates = 0;
-  if (k4j_mode_of(P->flags, route_env()) < 0 && out_len0 == 0) {
-    const uint32_t k4j_min = P->nframes <= K4J_FEW_FRAMES ? K4J_MIN_BLOCKS_FEW : K4J_MIN_BLOCKS;
+  if (plan_k4j_counts(P->flags, route_env(), P->prefix, P->chain, out_len0)) {
+    const uint32_t k4j_min = P->k4j_min();
     for (const HostPart& hp : P->parts)
       for (const HostFrame& hf : hp.frames) j_candidates += hf.key == KEY_NONE && hf.ncomp >= k4j_min;
   }
@@ -1355,7 +1361,7 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
   const HostBlock* d_blocks = (const HostBlock*)(B.d_out + B.fb);
   P->nframes = F;
   P->cus = device_cus();
-  const uint32_t k4j_min = F <= K4J_FEW_FRAMES ? K4J_MIN_BLOCKS_FEW : K4J_MIN_BLOCKS;
+  const uint32_t k4j_min = P->k4j_min();
   const uint64_t nt = (F + 255) / 256;
   if (!B.d_shape && hipMalloc(&B.d_shape, sizeof(PlanShape)) != hipSuccess) return ZD_E_HIP;
   if (!B.h_small && hipHostMalloc((void**)&B.h_small, 64 * 8, hipHostMallocDefault) != hipSuccess) return ZD_E_HIP;
@@ -1378,7 +1384,7 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
   const DictData* D = P->dict.get();
   const bool tabs = D && !D->raw;
   PlanCtx X = plan_ctx(P, tabs ? 0 : -1, tabs ? pre : none, D ? D->content : 0, D ? D->rep : rep0, 0, shape.multi == 0,
-                       k4j_mode_of(P->flags, route_env()) < 0 ? shape.jcand : 0);
+                       plan_k4j_counts(P->flags, route_env(), P->prefix, P->chain, 0) ? shape.jcand : 0);
   if (in) { X.place_out = in->place_out; X.place_cap = in->place_cap; }
   if (P->dset) {
     if (!in || !in->d_dset) return ZD_E_INVALID_ARG;
@@ -2982,7 +2988,7 @@ static int batch_create(const BatchSpec& S, zd_batch** out) {
     P->d_chain_order = B->d_order;
     P->d_chain_parent = B->d_par;
     P->chain_count = B->chain_count;
-    // ZD_F_CHAIN_BLOCK_PARALLEL: what the planners number the J frames level-major from
+    // ZD_F_CHAIN_BLOCK_PARALLEL, ZD_F_AUTO_EXECUTOR: what the planners number the J frames level-major from
     if (P->chain_on_j()) {
       if (S.on_device) P->d_chain_lcount = B->d_lcount;
       else P->h_chain_order.assign(H.chain.begin() + n, H.chain.end());
@@ -3157,7 +3163,10 @@ int zd_batch_info_get(const zd_batch* B, zd_batch_info* info) {
 
 int zd_batch_info_get_sized(const zd_batch* B, zd_batch_info* info, size_t info_bytes) {
   if (!B || !info || info_bytes < offsetof(zd_batch_info, prefix_bytes_total)) return ZD_E_INVALID_ARG;
-  memcpy(info, &B->info, std::min(info_bytes, sizeof(zd_batch_info)));
+  zd_batch_info2 I{};
+  I.info = B->info;
+  I.k4j_chunks = B->P ? B->P->n_jframes : 0;   // (the plan's total, which both planners bring back)
+  memcpy(info, &I, std::min(info_bytes, sizeof I));
   return ZD_OK;
 }
 
@@ -3222,7 +3231,7 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
       if (key_code(k) == ZD_E_OUT_OF_DOMAIN && key_phase(k) == PH_LIMIT && key_stage(k) == LS_JROUNDS)
         redo.push_back(i);
     }
-    // a chain batch (K4J only with ZD_F_CHAIN_BLOCK_PARALLEL): every chunk behind
+    // a chain batch (K4J only with ZD_F_CHAIN_BLOCK_PARALLEL or ZD_F_AUTO_EXECUTOR): every chunk behind
     // such a chunk goes with it -- the launch left them ZD_E_NOT_DECODED -- as one
     // streaming chain batch over that set, the parents remapped.  A chunk of the
     // set whose parent is outside it (the parent decoded fine) is a root there:
@@ -3266,7 +3275,7 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
         dst[k] = (void*)(uintptr_t)B->dst[i];
         dc[k] = B->dst_cap[i];
       }
-      // a prefix batch (K4J only with ZD_F_BLOCK_PARALLEL): the redo chunks'
+      // a prefix batch (K4J only with ZD_F_BLOCK_PARALLEL or ZD_F_AUTO_EXECUTOR): the redo chunks'
       // checked prefix addresses and sizes go with them -- a chunk whose prefix
       // plus capacity the streaming executor cannot hold ends ZD_E_OUT_OF_DOMAIN.
       // (plan_ctx turns K4J off for every dictionary and set plan, so such a
@@ -3291,7 +3300,8 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
       if (P->prefix) { S.prefix = pf.data(); S.prefix_bytes = pz.data(); }
       if (B->chain) { S.chain = true; S.parent = rpar.data(); }
       S.n = m;
-      S.flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_CHAIN_BLOCK_PARALLEL | ZD_F_J_ONE_ROUND)) | ZD_F_FRAME_SERIAL;
+      S.flags = (B->flags & ~(ZD_F_BLOCK_PARALLEL | ZD_F_CHAIN_BLOCK_PARALLEL | ZD_F_AUTO_EXECUTOR | ZD_F_J_ONE_ROUND)) |
+                ZD_F_FRAME_SERIAL;
       S.dict = B->dict;
       S.dset = B->dset;
       S.stream = s;

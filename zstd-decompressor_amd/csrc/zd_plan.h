@@ -7,6 +7,7 @@
 
 #include "../../include/zd.h"
 #include "zd_common.h"
+#include "zd_route.h"
 #include "zd_walk.h"
 
 namespace zd {
@@ -78,6 +79,12 @@ struct PlanCtx {
   bool fused;              // zd_k_fused plan: no K4F, 128-byte aligned literal and record slots
   int k4j_mode;
   uint32_t k4j_min;        // compressed blocks a frame needs for K4J (automatic mode)
+  // ZD_F_AUTO_EXECUTOR in a prefix or chain batch without a forcing flag
+  // (zd_route.h auto_exec; k4j_mode is 0 then): each frame is routed by
+  // plan_auto_j, with k4j_min the rule's minimum at the batch's width
+  // (auto_min_blocks) and k4j_auto its candidates within the cap
+  // (auto_candidates_ok); a chain batch has j_at below as well
+  bool auto_exec;
   // A dictionary plan (zd_plan_create_dict): out_len0 is the dictionary's
   // content size, positions before the frame that live in the dictionary's
   // buffer, not in the output: a frame's region starts at its own first byte
@@ -112,17 +119,44 @@ struct PlanCtx {
   // k4j_mode 1 (a batch created with ZD_F_BLOCK_PARALLEL, no chain: zd_route.h
   // k4j_mode_behind; a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL:
   // k4j_mode_plan, with j_at below) every such frame with a compressed block
-  // goes to K4J.
+  // goes to K4J; with auto_exec the frames that plan_auto_j names.
   const uint64_t* prefix_bytes;
-  // Optional K4J numbering (a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL;
-  // null everywhere else): frame fi's K4J entries start at j_at[PLAN_J_COLS * fi
-  // ...] -- its JFrame, first J block, first segment, first state word, first
+  // Optional K4J numbering (a chain batch created with ZD_F_CHAIN_BLOCK_PARALLEL
+  // or routed by ZD_F_AUTO_EXECUTOR; null everywhere else): frame fi's K4J
+  // entries start at j_at[PLAN_J_COLS * fi ...] -- its JFrame, first J block, first segment, first state word, first
   // piece (PlanJ order) -- instead of at the running counts, so that the J
   // frames are numbered level-major (plan_j_order) and every level of the chain
   // owns one contiguous range of each.  The running counts advance as ever
   // (the totals, and the per-frame counts that plan_j_order scans).
   const uint64_t* j_at;
 };
+
+// The K4J fields of a plan's PlanCtx from its flags and shape (plan_ctx; host
+// only).  `width`: the chunks that execute together, what ZD_F_AUTO_EXECUTOR's
+// minimum reads (a prefix batch's count, a chain batch's widest level; unused
+// elsewhere).  plan_k4j_min is known before the walk's frames are looked at;
+// `candidates` are the frames without a walk-found error and with at least that
+// many compressed blocks, counted where plan_k4j_counts says a rule reads them.
+inline uint32_t plan_k4j_min(uint32_t flags, bool prefix, bool chain, uint64_t nframes, uint64_t width) {
+  return auto_exec(flags, prefix, chain) ? auto_min_blocks(width)
+         : nframes <= K4J_FEW_FRAMES    ? K4J_MIN_BLOCKS_FEW
+                                        : K4J_MIN_BLOCKS;
+}
+inline bool plan_k4j_counts(uint32_t flags, const RouteEnv& E, bool prefix, bool chain, uint64_t out_len0) {
+  return auto_exec(flags, prefix, chain) || (k4j_mode_of(flags, E) < 0 && out_len0 == 0);
+}
+inline void plan_k4j_fields(PlanCtx& X, uint32_t flags, const RouteEnv& E, bool dict, bool prefix, bool chain,
+                            uint64_t out_len0, uint64_t nframes, uint64_t width, uint64_t candidates) {
+  X.k4j_mode = k4j_mode_of(flags, E);
+  X.k4j_min = plan_k4j_min(flags, prefix, chain, nframes, width);
+  X.k4j_auto = X.k4j_mode < 0 && out_len0 == 0 && candidates > 0 && candidates <= K4J_MAX_FRAMES;
+  X.auto_exec = false;
+  if (dict) {
+    X.auto_exec = auto_exec(flags, prefix, chain);
+    X.k4j_auto = X.auto_exec && auto_candidates_ok(candidates);
+    X.k4j_mode = k4j_mode_plan(X.k4j_mode, flags, true, prefix, chain);
+  }
+}
 
 // The K4J columns of PlanCounts, in j_at's order
 constexpr int PLAN_J_COLS = 5;
@@ -167,6 +201,15 @@ inline void plan_j_levels(const uint64_t* start, const uint32_t* count, uint32_t
     lev[l] = JLevel{s[0], end[0] - s[0], s[1], end[1] - s[1], s[2], end[2] - s[2]};
     end[0] = s[0]; end[1] = s[1]; end[2] = s[2];
   }
+}
+
+// ZD_F_AUTO_EXECUTOR's rule for one frame that K4J could take behind a prefix
+// (plan_frame's j_ok): (a) at least min_blocks compressed blocks while the
+// batch's candidates are within the cap (cand_ok), or (b) a frame the streaming
+// executor's int32 positions cannot hold behind its prefix.  The one copy of the
+// rule: both planners take it from plan_frame.
+ZD_HD inline bool plan_auto_j(uint32_t ncomp, uint32_t min_blocks, bool cand_ok, uint64_t prefix, uint64_t cap) {
+  return (cand_ok && ncomp >= min_blocks) || (prefix <= K4_MAX_FRAME_OUT && prefix + cap > K4_MAX_FRAME_OUT);
 }
 
 // The entry of Dictionary_ID id (non-zero) in a table sorted by ID, or -1.
@@ -369,9 +412,12 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   // (K4 truncates out_len0 to 32 bits).  A frame that a prefix batch created
   // with ZD_F_BLOCK_PARALLEL sends to K4J keeps only the prefix's own limit:
   // K4J's state words number the frame's own bytes from 0 and never hold a
-  // prefix position
-  const bool j_pfx = X.prefix_bytes && X.k4j_mode == 1 && !frame_failed_host && fd.nblocks && hf.ncomp &&
-                     hf.d.kind == ZD_FRAME_ZSTD && cap <= K4J_MAX_FRAME_OUT;
+  // prefix position.  ZD_F_AUTO_EXECUTOR (j_auto): of the frames the flag could
+  // send there, those the rule names
+  const bool j_ok = X.prefix_bytes && !frame_failed_host && fd.nblocks && hf.ncomp && hf.d.kind == ZD_FRAME_ZSTD &&
+                    cap <= K4J_MAX_FRAME_OUT;
+  const bool j_auto = X.auto_exec && j_ok && plan_auto_j(hf.ncomp, X.k4j_min, X.k4j_auto, out_len0, cap);
+  const bool j_pfx = j_ok && (X.k4j_mode == 1 || j_auto);
   if (X.prefix_bytes && out_len0 &&
       (out_len0 > K4_MAX_FRAME_OUT || (!j_pfx && cap + out_len0 > K4_MAX_FRAME_OUT))) {
     fs.key = plan_min(fs.key, make_key(PH_LIMIT, 0, 0, 0, ZD_E_OUT_OF_DOMAIN));
@@ -385,8 +431,8 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   // request (j_pfx: the scatter writes the bytes that come from the prefix)
   const bool to_j = (out_len0 == 0 || j_pfx) && !frame_failed_host && fd.nblocks && hf.ncomp && hf.d.kind == ZD_FRAME_ZSTD &&
                     cap <= K4J_MAX_FRAME_OUT &&
-                    (X.k4j_mode >= 0 ? X.k4j_mode == 1
-                                     : ((X.k4j_auto && hf.ncomp >= X.k4j_min) || cap > K4_MAX_FRAME_OUT));
+                    (j_auto || (X.k4j_mode >= 0 ? X.k4j_mode == 1
+                                                : ((X.k4j_auto && hf.ncomp >= X.k4j_min) || cap > K4_MAX_FRAME_OUT)));
   // larger frames with sequences that K4J does not take (forced off, or past
   // its 32 GiB) are outside the GPU path's domain
   if (!to_j && cap + (X.dict ? out_len0 : 0) > K4_MAX_FRAME_OUT && seqs_in_frame)

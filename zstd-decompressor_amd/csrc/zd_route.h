@@ -104,6 +104,22 @@ inline bool chain_j(uint32_t flags, bool chain) { return chain && (flags & ZD_F_
 inline int k4j_mode_plan(int mode, uint32_t flags, bool dict, bool prefix, bool chain) {
   return chain_j(flags, chain) ? 1 : k4j_mode_behind(mode, flags, dict, prefix, chain);
 }
+// ZD_F_AUTO_EXECUTOR holds: a prefix or chain batch (`prefix`: both) without the
+// forcing flags of its kind -- each frame is routed by plan_auto_j (zd_plan.h),
+// the plan's mode stays 0.  The flag means nothing anywhere else.
+inline bool auto_exec(uint32_t flags, bool prefix, bool chain) {
+  return prefix && (flags & ZD_F_AUTO_EXECUTOR) &&
+         !(flags & (chain ? ZD_F_CHAIN_BLOCK_PARALLEL : ZD_F_BLOCK_PARALLEL | ZD_F_FRAME_SERIAL));
+}
+// A chain batch laid out for K4J level by level (J frames numbered level-major,
+// launches and pend words per level): forced or automatic
+inline bool chain_j_layout(uint32_t flags, bool chain) { return chain_j(flags, chain) || (chain && auto_exec(flags, true, true)); }
+// The automatic rule's block minimum at a width (the chunks that execute
+// together: a prefix batch's count, a chain batch's widest level)
+inline uint32_t auto_min_blocks(uint64_t width) {
+  return width <= ZD_AUTO_FEW_CHUNKS ? ZD_AUTO_MIN_BLOCKS_FEW : ZD_AUTO_MIN_BLOCKS;
+}
+inline bool auto_candidates_ok(uint64_t candidates) { return candidates > 0 && candidates <= ZD_AUTO_MAX_CANDIDATES; }
 
 // What a plan is built for (plan_ctx).  `in` as route_plan's, its `context` set
 // for a dictionary or dictionary-set plan too (`dict`): the streaming executor only.

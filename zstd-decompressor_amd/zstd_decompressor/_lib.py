@@ -67,6 +67,12 @@ class BatchInfoEx(BatchInfo):
     _fields_ = [("prefix_bytes_total", C.c_uint64)]
 
 
+class BatchInfo2(BatchInfoEx):
+    """zd_batch_info2: what zd_batch_info_get_sized writes behind zd_batch_info
+    when the caller's size covers it."""
+    _fields_ = [("k4j_chunks", C.c_uint64)]
+
+
 COMM_ID_BYTES = 128
 
 # every entry point declared in include/zd.h: name -> (restype, argtypes)
@@ -273,6 +279,7 @@ F_K1_SPLIT = 512       # K1 as a parse pass and a build pass in a plan of any si
 F_VERIFY_CHECKSUM = 1024  # Content_Checksums verified inside the decode launch (zd_k_verify): CHECKSUM_WRONG
 F_LONG_WINDOW = 2048   # accept a Window_Size up to 2 GiB (default: the reference's 8 MiB limit)
 F_CHAIN_BLOCK_PARALLEL = 4096  # a chain batch (parents=): frames with a compressed block -> K4J, level by level
+F_AUTO_EXECUTOR = 8192  # a prefix or chain batch: each chunk's executor by rule (include/zd.h ZD_AUTO_*)
 SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
 SIZES_LONG_WINDOW = 2048  # zd_chunk_sizes_device: the chunks will be decoded with F_LONG_WINDOW (the same bit)
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)

@@ -327,7 +327,7 @@ def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, str
 
 
 def _batch_info(h):
-    info = _lib.BatchInfoEx()
+    info = _lib.BatchInfo2()
     _lib.check(_lib.lib().zd_batch_info_get_sized(h, C.byref(info), C.sizeof(info)), "zd_batch_info_get_sized")
     return info
 
@@ -356,6 +356,9 @@ class Batch:
     decoded output OF THE SAME LAUNCH is chunk i's prefix (its prefix size must
     then be 0; prefixes may be None when no chunk has an external one).  A chunk
     behind a failed ancestor is NOT_DECODED; `chain_info` gives the levels).
+    flags: with prefixes= or parents=, _lib.F_AUTO_EXECUTOR routes each chunk's
+    frame on its own (large frames to the block-parallel executor, the rest to
+    the streaming one); `info.k4j_chunks` counts the former in any batch.
 
     src_ptrs / dst_ptrs are device addresses (integers, e.g. tensor.data_ptr()),
     src_sizes / dst_caps byte counts.  A chunk holds one zstd frame (skippable
