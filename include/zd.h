@@ -81,6 +81,9 @@ extern "C" {
                                       (a dictionary set: an ID the set does not hold) */
 #define ZD_E_CHECKSUM_WRONG  (-100) /* ZD_F_VERIFY_CHECKSUM: the frame decoded, and its bytes do not hash to its
                                        Content_Checksum (libzstd: "Restored data doesn't match checksum") */
+#define ZD_E_SEEK_TABLE      (-101) /* a seekable archive's seek table contradicts itself or the archive
+                                       (zd_seekable_open_device); a range of a read: a frame decoded to another
+                                       length than the table's Decompressed_Size */
 
 /* Device workspaces of destroyed plans are kept for reuse by later plans of
  * the process (bounded by ZD_WS_CACHE_MB, default 8 GiB; 0 disables it).
@@ -987,6 +990,129 @@ int  zd_batch_results(zd_batch* batch, void* stream, int32_t* status, uint64_t* 
  * (matches / differs / no Content_Checksum or not decoded), hash[i] = XXH64. */
 int  zd_batch_checksums(zd_batch* batch, void* stream, int32_t* ok, uint64_t* hash);
 void zd_batch_destroy(zd_batch* batch);
+
+/* ------------------------------------------------------------------ */
+/* Random access (beyond the reference): byte ranges of a zstd          */
+/* SEEKABLE archive that lies on the device.  A seekable archive is an  */
+/* ordinary multi-frame .zst whose last frame is a skippable frame      */
+/* holding a seek table: every entry's compressed and decompressed size */
+/* and, optionally, a checksum (csrc/zd_seek.h restates the layout).    */
+/* An entry is treated as a batch chunk: one zstd frame with any number */
+/* of skippable frames around it; an entry of two zstd frames is that   */
+/* chunk's ZD_E_OUT_OF_DOMAIN, as in any batch (a documented limit).    */
+/* Limits: no dictionary, prefix or chain reads; the table's own        */
+/* per-entry checksums are exposed, not verified; a read's destinations */
+/* cannot be re-pointed; the ranges come as device arrays only; nothing */
+/* of this in zd_plan_*, the sharded calls or zd_context.               */
+/* ------------------------------------------------------------------ */
+typedef struct zd_seekable zd_seekable;
+typedef struct zd_seek_read zd_seek_read;
+
+typedef struct zd_seekable_info {
+  uint64_t nframes;            /* entries of the seek table */
+  uint64_t content_bytes;      /* the sum of the Decompressed_Sizes */
+  uint64_t compressed_bytes;   /* the sum of the Compressed_Sizes: the archive without its table */
+  uint64_t table_bytes;        /* the seek table's frame: header, entries, footer */
+  uint32_t has_checksums;      /* the entries carry a Checksum */
+  uint32_t max_frame_content;  /* the largest Decompressed_Size */
+} zd_seekable_info;
+
+/* Opens the archive of n bytes at device address d_archive.  The last 9
+ * bytes come to the host (one small copy, one wait) and are checked; then
+ * zd_k_seek_table reads the entries where they lie -- at any alignment,
+ * never outside the table -- into three device arrays the object owns,
+ * c_off[nframes + 1] and d_off[nframes + 1] (u64: entry f occupies archive
+ * bytes [c_off[f], c_off[f + 1]) and holds content bytes [d_off[f],
+ * d_off[f + 1]); the sums cannot wrap at any legal table) and
+ * checksum[nframes] (u32, when present), and checks the skippable header;
+ * one more wait brings back the two totals and the header's verdict.  Two
+ * host waits on `stream` in all.
+ *   ZD_E_NOT_ENOUGH_BYTES    n < 17 (before any HIP call); a table larger
+ *                            than the archive
+ *   ZD_E_UNRECOGNIZED_MAGIC  the footer's or the skippable header's magic
+ *   ZD_E_FRAME_RESERVED_SET  reserved descriptor bits set
+ *   ZD_E_OUT_OF_DOMAIN       more than 2^27 entries
+ *   ZD_E_SEEK_TABLE          Frame_Size is not nframes * entry_bytes + 9, or
+ *                            the compressed sizes do not sum to exactly the
+ *                            bytes before the table
+ *   ZD_E_INVALID_ARG         d_archive or out NULL (before any HIP call)
+ * The archive must stay valid and unchanged until zd_seekable_close: it is
+ * read here and at each read's creation, never by a decode.  It needs no
+ * padding. */
+int  zd_seekable_open_device(const void* d_archive, size_t n, void* stream, zd_seekable** out);
+int  zd_seekable_info_get(const zd_seekable* z, zd_seekable_info* info);
+/* The three device arrays, for callers that plan their own reads; the object
+ * owns them (d_checksum: NULL without checksums; any pointer may be NULL). */
+int  zd_seekable_table(const zd_seekable* z, const uint64_t** d_c_off, const uint64_t** d_d_off,
+                       const uint32_t** d_checksum);
+/* Reads made from the archive stay usable; no new read can be made. */
+void zd_seekable_close(zd_seekable* z);
+
+/* A read of nranges ranges: range i is content bytes [d_off[i], d_off[i] +
+ * d_len[i]), clamped to the content's end as pread clamps (a range that
+ * starts at or past the end, or of length 0, is ZD_OK with length 0), and is
+ * written to [d_dst[i], d_dst[i] + clamped length): no other byte is written,
+ * d_dst[i] may have any alignment.  The three arrays are DEVICE arrays of
+ * nranges entries, readable on `stream`; they may be released when the call
+ * returns.  A NULL d_dst[i] with a non-zero clamped length, or an address range
+ * that wraps, makes that range ZD_E_INVALID_ARG, alone (it needs no frame:
+ * nothing is read or written for it).  Overlapping
+ * destinations are the caller's duty, as in zd_batch_create_device.
+ * flags: a plain batch's flags, handed to the inner batch
+ * (ZD_F_VERIFY_CHECKSUM verifies the frames' own Content_Checksums,
+ * ZD_F_LONG_WINDOW works); ZD_F_SKIPPABLE is ZD_E_INVALID_ARG.
+ * ZD_E_INVALID_ARG for the whole call, before any HIP call: out NULL, a NULL
+ * array with nranges > 0, nranges >= 2^31, unknown flag bits, a NULL archive
+ * (what a closed one's handle is to its owner: the Python mirror passes it).
+ * Every needed frame is decoded once per launch, however many ranges touch
+ * it.  A frame that lies wholly inside exactly one range decodes IN PLACE, at
+ * d_dst[i] + (d_off[f] - off_i) with capacity Decompressed_Size: a sequential
+ * read of a long range stages nothing but its two edge frames.  Every other
+ * needed frame -- a partial frame at a range's edge, a frame more than one
+ * range touches -- decodes into a staging buffer the read owns (offsets
+ * rounded to 16, from the workspace cache).  Built on the GPU
+ * (zd_k_seek_cover, zd_k_seek_mark, zd_k_seek_plan, the scans,
+ * zd_k_seek_chunks) and handed to the device creation of a batch.  Host waits:
+ * one of its own (the needed frames, the staging bytes, the 32 KiB copy pieces
+ * come back) and those of zd_batch_create_device, none more.
+ * ZD_E_OUT_OF_DOMAIN for the whole call: 2^31 copy pieces or more. */
+int  zd_seekable_read_create(zd_seekable* z, const uint64_t* d_off, const uint64_t* d_len,
+                             void* const* d_dst, size_t nranges, uint32_t flags,
+                             void* stream, zd_seek_read** out);
+/* Queues, in this order: the inner batch's decode; zd_k_seek_finish, which
+ * copies the staged frames' wanted parts to the ranges' destinations (the
+ * grid runs over 32 KiB pieces of the destinations; in-place frames are
+ * skipped; nothing outside the staging buffer is read, nothing outside the
+ * destination ranges written); the result pass, the last launch.  Range i's
+ * status is that of the lowest-numbered of its frames that did not end ZD_OK;
+ * with every frame ZD_OK but one whose decoded length differs from its
+ * Decompressed_Size, ZD_E_SEEK_TABLE; else ZD_OK.  Its length is the clamped
+ * length, or 0 on failure; a failed range's destination bytes are unspecified.
+ * No allocation, no host synchronisation: capturable, and may be called again. */
+int  zd_seek_read_decode_async(zd_seek_read* r, void* stream);
+/* The finish and result passes alone, behind whatever `stream` holds: what
+ * zd_seek_read_results runs after the inner batch's own results, for a caller
+ * that reads the inner batch's state itself, and what a timing run puts between
+ * two events.  ZD_E_INVALID_ARG before the first zd_seek_read_decode_async. */
+int  zd_seek_read_finish_async(zd_seek_read* r, void* stream);
+/* The per-range device arrays (nranges entries each), owned by the read. */
+int  zd_seek_read_device_results(const zd_seek_read* r, const int32_t** d_status, const uint64_t** d_len);
+/* Waits and returns the same on the host (arrays of cap >= nranges entries,
+ * either may be NULL) and the number of ranges that are not ZD_OK.  Runs the
+ * inner zd_batch_results -- a K4J frame that did not converge is decoded again
+ * there -- and then the finish and result passes once more. */
+int  zd_seek_read_results(zd_seek_read* r, void* stream, int32_t* status, uint64_t* len, size_t cap,
+                          uint64_t* nfailed);
+typedef struct zd_seek_read_info {
+  uint64_t nranges;
+  uint64_t frames_decoded;     /* distinct needed entries: the inner batch's chunks */
+  uint64_t frames_in_place;    /*   of them, decoded at a range's own destination */
+  uint64_t staged_bytes;       /* the staging buffer (every staged frame rounded up to 16) */
+  uint64_t copy_pieces;        /* zd_k_seek_finish's grid: 32 KiB pieces of the destinations */
+  zd_batch_info2 batch;        /* the inner batch (zeroed when no frame is needed) */
+} zd_seek_read_info;
+int  zd_seek_read_info_get(const zd_seek_read* r, zd_seek_read_info* info);
+void zd_seek_read_destroy(zd_seek_read* r);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: frame-range sharding + RCCL gather.      */

@@ -28,6 +28,7 @@
 #include "zd_internal.h"
 #include "zd_launch.h"
 #include "zd_plan.h"
+#include "zd_seek.h"
 #include "zd_walk.h"
 
 using namespace zd;
@@ -1720,6 +1721,7 @@ const char* zd_status_name(int s) {
     case ZD_E_DICT_CORRUPTED: return "DictionaryCorrupted";
     case ZD_E_DICT_MISMATCH: return "DictionaryMismatch";
     case ZD_E_CHECKSUM_WRONG: return "ChecksumWrong";
+    case ZD_E_SEEK_TABLE: return "SeekTableWrong";
     default: return "Unknown";
   }
 }
@@ -3366,6 +3368,265 @@ int zd_batch_checksums(zd_batch* B, void* stream, int32_t* ok, uint64_t* hash) {
     if (ok) ok[i] = have ? ((uint32_t)h[i] == d.checksum ? 1 : 0) : -1;
     if (hash) hash[i] = done ? h[i] : 0;
   }
+  return ZD_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Seekable archives (zd_seekable_*): the seek table as three device arrays,
+// and reads -- R byte ranges of the content -- as an ordinary device-built
+// batch over the needed entries, whose chunk table zd_seek.hip's kernels
+// write, plus the pass that delivers the staged frames' bytes.  The rules are
+// zd_seek.h's.
+// ===========================================================================
+namespace {
+struct SeekData {
+  int dev = -1;
+  const uint8_t* d_archive = nullptr;
+  uint64_t n = 0;
+  SeekFooter ft;
+  uint8_t* d_mem = nullptr;              // one allocation: c_off | d_off | scan words | res | checksum
+  uint64_t *c_off = nullptr, *d_off = nullptr;
+  uint32_t* checksum = nullptr;
+  zd_seekable_info info{};
+  ~SeekData() { if (d_mem) (void)hipFree(d_mem); }
+};
+constexpr uint32_t SEEK_READ_FLAGS =
+    ZD_F_BLOCK_PARALLEL | ZD_F_FRAME_SERIAL | ZD_F_SEQ_ONE_LANE | ZD_F_NO_FUSE | ZD_F_K1_LANES | ZD_F_J_ONE_ROUND |
+    ZD_F_SEQ_NO_LATENCY | ZD_F_K1_SPLIT | ZD_F_VERIFY_CHECKSUM | ZD_F_LONG_WINDOW | ZD_F_CHAIN_BLOCK_PARALLEL |
+    ZD_F_AUTO_EXECUTOR;
+uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
+}  // namespace
+
+struct zd_seekable {
+  std::shared_ptr<SeekData> p;
+};
+
+struct zd_seek_read {
+  std::shared_ptr<SeekData> a;           // (a read outlives zd_seekable_close: d_off is read at every launch)
+  zd_batch* B = nullptr;                 // the needed entries; null: none
+  int dev = -1;
+  uint8_t* d_mem = nullptr;              // one allocation for A's arrays, the scan words and res
+  SeekRead A{};
+  uint8_t* d_stage = nullptr;            // the staged frames, from the workspace cache
+  uint64_t stage_alloc = 0;
+  uint64_t npieces = 0;
+  bool launched = false;
+  zd_seek_read_info info{};
+};
+
+extern "C" {
+
+int zd_seekable_open_device(const void* d_archive, size_t n, void* stream, zd_seekable** out) {
+  if (!out) return ZD_E_INVALID_ARG;
+  if (n < SEEK_MIN_BYTES) return ZD_E_NOT_ENOUGH_BYTES;
+  if (!d_archive) return ZD_E_INVALID_ARG;
+  const hipStream_t s = (hipStream_t)stream;
+  const uint8_t* base = (const uint8_t*)d_archive;
+  // ---- the footer: one small copy, one wait ----
+  uint8_t last[SEEK_FOOTER_BYTES];
+  HIPCHK(hipMemcpyAsync(last, base + (n - SEEK_FOOTER_BYTES), SEEK_FOOTER_BYTES, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  SeekFooter ft;
+  if (int r = seek_footer(last, n, &ft)) return r;
+  std::shared_ptr<SeekData> D(new (std::nothrow) SeekData());
+  if (!D) return ZD_E_NO_MEMORY;
+  HIPCHK(hipGetDevice(&D->dev));
+  D->d_archive = base;
+  D->n = n;
+  D->ft = ft;
+  // ---- the entries, where they lie; the sums; the header's verdict ----
+  const uint64_t F = ft.nframes, n1 = F + 1, tiles = (n1 + 255) / 256;
+  const uint64_t o_tot = 2 * n1 * 8, o_res = o_tot + 2 * (tiles + 1) * 8, o_sum = o_res + 4 * 8;
+  HIPCHK(hipMalloc(&D->d_mem, o_sum + std::max<uint64_t>(F, 1) * 4));
+  D->c_off = (uint64_t*)D->d_mem;
+  D->d_off = D->c_off + n1;
+  uint64_t* tot = (uint64_t*)(D->d_mem + o_tot);
+  uint64_t* res = (uint64_t*)(D->d_mem + o_res);
+  D->checksum = ft.checksums ? (uint32_t*)(D->d_mem + o_sum) : nullptr;
+  HIPCHK(launch_seek_table(base + (n - ft.table_bytes), ft, D->c_off, D->d_off, D->checksum, tot, res, s));
+  uint64_t h[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(h, res, 2 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h + 2, D->c_off + F, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h + 3, D->d_off + F, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (const int r = (int)(int64_t)h[0]) return r;
+  if (const int r = seek_sums(h[2], n, ft)) return r;
+  zd_seekable_info& I = D->info;
+  I.nframes = F;
+  I.content_bytes = h[3];
+  I.compressed_bytes = h[2];
+  I.table_bytes = ft.table_bytes;
+  I.has_checksums = ft.checksums;
+  I.max_frame_content = (uint32_t)h[1];
+  zd_seekable* z = new (std::nothrow) zd_seekable();
+  if (!z) return ZD_E_NO_MEMORY;
+  z->p = std::move(D);
+  *out = z;
+  return ZD_OK;
+}
+
+int zd_seekable_info_get(const zd_seekable* z, zd_seekable_info* info) {
+  if (!z || !z->p || !info) return ZD_E_INVALID_ARG;
+  *info = z->p->info;
+  return ZD_OK;
+}
+
+int zd_seekable_table(const zd_seekable* z, const uint64_t** d_c_off, const uint64_t** d_d_off,
+                      const uint32_t** d_checksum) {
+  if (!z || !z->p) return ZD_E_INVALID_ARG;
+  if (d_c_off) *d_c_off = z->p->c_off;
+  if (d_d_off) *d_d_off = z->p->d_off;
+  if (d_checksum) *d_checksum = z->p->checksum;
+  return ZD_OK;
+}
+
+void zd_seekable_close(zd_seekable* z) { delete z; }
+
+void zd_seek_read_destroy(zd_seek_read* r) {
+  if (!r) return;
+  if (r->launched) (void)hipDeviceSynchronize();   // (the passes behind the batch's own work read the staging buffer)
+  if (r->B) zd_batch_destroy(r->B);
+  ws_release(r->d_stage, r->stage_alloc, r->dev);
+  if (r->d_mem) (void)hipFree(r->d_mem);
+  delete r;
+}
+
+int zd_seekable_read_create(zd_seekable* z, const uint64_t* d_off, const uint64_t* d_len, void* const* d_dst,
+                            size_t nranges, uint32_t flags, void* stream, zd_seek_read** out) {
+  // ---- argument checks: no HIP call before they are done (z is looked at last) ----
+  if (!out || (flags & ZD_F_SKIPPABLE) || (flags & ~(SEEK_READ_FLAGS | ZD_F_SKIPPABLE)) || nranges >= (1ull << 31))
+    return ZD_E_INVALID_ARG;
+  if (nranges && (!d_off || !d_len || !d_dst)) return ZD_E_INVALID_ARG;
+  if (!z || !z->p) return ZD_E_INVALID_ARG;
+  struct DropRead { void operator()(zd_seek_read* r) const { zd_seek_read_destroy(r); } };
+  std::unique_ptr<zd_seek_read, DropRead> hold(new (std::nothrow) zd_seek_read());
+  zd_seek_read* r = hold.get();
+  if (!r) return ZD_E_NO_MEMORY;
+  r->a = z->p;
+  r->info.nranges = nranges;
+  if (!nranges) { *out = hold.release(); return ZD_OK; }
+  const SeekData& D = *r->a;
+  int dev = -1;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev != D.dev) return ZD_E_INVALID_ARG;
+  r->dev = dev;
+  const hipStream_t s = (hipStream_t)stream;
+  // ---- the read's arrays ----
+  const uint64_t R = nranges, F = D.ft.nframes;
+  const uint64_t tilesF = (F + 255) / 256, tilesR = (R + 1 + 255) / 256;
+  uint64_t o = 0;
+  const auto take = [&](uint64_t bytes) { const uint64_t at = o; o += up16(bytes); return at; };
+  const uint64_t o_off = take(8 * R), o_len = take(8 * R), o_dst = take(8 * R), o_piece = take(8 * (R + 1)),
+                 o_olen = take(8 * R), o_idx = take(2 * 8 * F), o_tot = take(8 * (2 * (tilesF + 1) + tilesR + 1)),
+                 o_res = take(8 * 4), o_f0 = take(4 * R), o_f1 = take(4 * R), o_st = take(4 * R),
+                 o_cover = take(4 * F), o_part = take(4 * F), o_bad = take(R);
+  HIPCHK(hipMalloc(&r->d_mem, o));
+  HIPCHK(hipMemsetAsync(r->d_mem, 0, o, s));
+  SeekRead& A = r->A;
+  uint8_t* m = r->d_mem;
+  A.off = (uint64_t*)(m + o_off); A.len = (uint64_t*)(m + o_len); A.dst = (uint64_t*)(m + o_dst);
+  A.piece0 = (uint64_t*)(m + o_piece);
+  A.f0 = (uint32_t*)(m + o_f0); A.f1 = (uint32_t*)(m + o_f1);
+  A.bad = m + o_bad;
+  A.status = (int32_t*)(m + o_st); A.out_len = (uint64_t*)(m + o_olen);
+  A.cover = (uint32_t*)(m + o_cover); A.partial = (uint32_t*)(m + o_part);
+  A.idx = (uint64_t*)(m + o_idx); A.soff = A.idx + F;
+  A.R = (uint32_t)R; A.F = (uint32_t)F;
+  uint64_t* tot = (uint64_t*)(m + o_tot);
+  uint64_t* res = (uint64_t*)(m + o_res);
+  // ---- clamp, search, cover counts, the scans; the one wait of this layer ----
+  HIPCHK(launch_seek_layout(d_off, d_len, (const uint64_t*)d_dst, D.d_off, A, tot, res, s));
+  uint64_t h[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(h, res, 4 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint64_t needed = h[0], staged = h[1];
+  r->npieces = h[2];
+  r->info.frames_decoded = needed;
+  r->info.frames_in_place = h[3];
+  r->info.staged_bytes = staged;
+  r->info.copy_pieces = r->npieces;
+  if (r->npieces >= (1ull << 31)) return ZD_E_OUT_OF_DOMAIN;    // zd_k_seek_finish's grid
+  if (!needed) { *out = hold.release(); return ZD_OK; }
+  // ---- the staging buffer, the chunk table, the inner batch ----
+  if (staged) HIPCHK(ws_alloc(dev, staged, &r->d_stage, &r->stage_alloc));
+  uint64_t* cols = nullptr;
+  HIPCHK(hipMalloc(&cols, 4 * 8 * needed));
+  std::unique_ptr<void, Free> cols_mem(cols);
+  HIPCHK(launch_seek_chunks(A, D.d_archive, D.c_off, D.d_off, r->d_stage, cols, cols + needed, cols + 2 * needed,
+                            cols + 3 * needed, s));
+  BatchSpec S{(const void* const*)cols, cols + needed, (void* const*)(cols + 2 * needed), cols + 3 * needed};
+  S.on_device = true; S.n = (size_t)needed; S.flags = flags; S.stream = s;
+  if (int e = batch_create(S, &r->B)) return e;
+  (void)zd_batch_info_get_sized(r->B, &r->info.batch.info, sizeof(zd_batch_info2));
+  *out = hold.release();
+  return ZD_OK;
+}
+
+// the finish and result passes, behind the inner batch's work on s
+static int seek_passes(zd_seek_read* r, hipStream_t s) {
+  const int32_t* b_status = nullptr;
+  const uint64_t* b_len = nullptr;
+  if (r->B) (void)zd_batch_device_results(r->B, &b_status, &b_len);
+  HIPCHK(launch_seek_finish(r->A, r->a->d_off, r->d_stage, r->npieces, s));
+  HIPCHK(launch_seek_results(r->A, r->a->d_off, b_status, b_len, s));
+  return 0;
+}
+
+int zd_seek_read_decode_async(zd_seek_read* r, void* stream) {
+  if (!r) return ZD_E_INVALID_ARG;
+  if (!r->A.R) return ZD_OK;
+  if (r->B)
+    if (int e = zd_batch_decode_async(r->B, stream)) return e;
+  if (int e = seek_passes(r, (hipStream_t)stream)) return e;
+  r->launched = true;
+  return ZD_OK;
+}
+
+int zd_seek_read_finish_async(zd_seek_read* r, void* stream) {
+  if (!r) return ZD_E_INVALID_ARG;
+  if (!r->A.R) return ZD_OK;
+  if (!r->launched) return ZD_E_INVALID_ARG;
+  return seek_passes(r, (hipStream_t)stream);
+}
+
+int zd_seek_read_device_results(const zd_seek_read* r, const int32_t** d_status, const uint64_t** d_len) {
+  if (!r) return ZD_E_INVALID_ARG;
+  if (d_status) *d_status = r->A.status;
+  if (d_len) *d_len = r->A.out_len;
+  return ZD_OK;
+}
+
+int zd_seek_read_results(zd_seek_read* r, void* stream, int32_t* status, uint64_t* len, size_t cap, uint64_t* nfailed) {
+  if (!r || ((status || len) && cap < r->A.R)) return ZD_E_INVALID_ARG;
+  if (nfailed) *nfailed = 0;
+  const size_t R = r->A.R;
+  if (!R) return ZD_OK;
+  if (!r->launched) return ZD_E_INVALID_ARG;
+  const hipStream_t s = (hipStream_t)stream;
+  if (r->B) {
+    // (a K4J frame that did not converge is decoded again in there: its bytes and
+    // its chunk's status are new, so the two passes run once more)
+    if (int e = zd_batch_results(r->B, stream, nullptr, nullptr, 0, nullptr)) return e;
+    if (int e = seek_passes(r, s)) return e;
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  std::vector<int32_t> st(R);
+  HIPCHK(hipMemcpy(st.data(), r->A.status, 4 * R, hipMemcpyDeviceToHost));
+  if (len) HIPCHK(hipMemcpy(len, r->A.out_len, 8 * R, hipMemcpyDeviceToHost));
+  uint64_t bad = 0;
+  for (size_t i = 0; i < R; i++) {
+    if (status) status[i] = st[i];
+    bad += st[i] != 0;
+  }
+  if (nfailed) *nfailed = bad;
+  return ZD_OK;
+}
+
+int zd_seek_read_info_get(const zd_seek_read* r, zd_seek_read_info* info) {
+  if (!r || !info) return ZD_E_INVALID_ARG;
+  *info = r->info;
   return ZD_OK;
 }
 

@@ -7302,3 +7302,7 @@ hipError_t launch_batch_fit(HostFrame* frames, const HostBlock* blocks, const ui
 }
 
 }  // namespace zd
+
+// The seekable-archive kernels (zd_k_seek_*), a file of their own compiled here:
+// libzd.so keeps one device code object.
+#include "zd_seek.hip"

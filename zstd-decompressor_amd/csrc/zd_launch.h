@@ -232,6 +232,56 @@ hipError_t launch_batch_fit(HostFrame* frames, const HostBlock* blocks, const ui
                             uint32_t n, uint8_t* bind, const uint32_t* set_ids, uint32_t nset, int32_t fallback,
                             uint8_t* used, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// Seekable archives (zd_seekable_*, zd_seek.hip; the rules: zd_seek.h)
+// ---------------------------------------------------------------------------
+struct SeekFooter;
+// zd_k_seek_table over the table at `table` (its skippable header's first
+// byte): c_off[f] / d_off[f] = entry f's sizes (nframes + 1 entries each, the
+// last 0; d_off == c_off + nframes + 1), checksum[f] when present, then the
+// two columns scanned into exclusive sums (tot: 2 x (tiles + 1) words).
+// res[0]: the header's verdict (a status), res[1]: the largest Decompressed_Size
+// (both zeroed here first).
+hipError_t launch_seek_table(const uint8_t* table, const SeekFooter& f, uint64_t* c_off, uint64_t* d_off,
+                             uint32_t* checksum, uint64_t* tot, uint64_t* res, hipStream_t s);
+
+// A read's device arrays (zd_seekable_read_create): R ranges over F frames.
+struct SeekRead {
+  // per range
+  uint64_t *off, *len;         // clamped (len 0: nothing to read, or a refused destination)
+  uint64_t* dst;
+  uint64_t* piece0;            // the range's first 32 KiB copy piece (exclusive scan; R + 1 entries)
+  uint32_t *f0, *f1;           // its first and last frame (len > 0)
+  uint8_t* bad;                // 1: ZD_E_INVALID_ARG
+  int32_t* status;             // the results
+  uint64_t* out_len;
+  // per frame
+  uint32_t *cover, *partial;   // ranges that touch the frame / that hold only a part of it
+  uint64_t *idx, *soff;        // the frame's chunk in the inner batch / its staging offset (soff == idx + F)
+  uint32_t R, F;
+};
+// zd_k_seek_cover (one lane a range: clamp, destination check, search, piece
+// count), zd_k_seek_mark (one wave a range: the cover counts), zd_k_seek_plan
+// (one lane a frame: needed, staged bytes), the scans (tot: 3 x (tiles + 1)
+// words, tiles of max(R + 1, F) entries) and zd_k_seek_totals: res[0..4) =
+// needed frames, staging bytes, copy pieces, frames in place.  cover, partial
+// and res are zeroed by the caller before.
+hipError_t launch_seek_layout(const uint64_t* off, const uint64_t* len, const uint64_t* dst, const uint64_t* d_off,
+                              const SeekRead& A, uint64_t* tot, uint64_t* res, hipStream_t s);
+// zd_k_seek_chunks: the inner batch's chunk table, four columns of `needed`
+// entries (src, size, dst, cap), one wave a range.
+hipError_t launch_seek_chunks(const SeekRead& A, const uint8_t* archive, const uint64_t* c_off, const uint64_t* d_off,
+                              uint8_t* staging, uint64_t* col_src, uint64_t* col_size, uint64_t* col_dst,
+                              uint64_t* col_cap, hipStream_t s);
+// zd_k_seek_finish: the staged frames' wanted parts to the destinations, one
+// workgroup a 32 KiB piece of a range.
+hipError_t launch_seek_finish(const SeekRead& A, const uint64_t* d_off, const uint8_t* staging, uint64_t npieces,
+                              hipStream_t s);
+// zd_k_seek_results: the ranges' statuses and lengths from the inner batch's
+// (b_status / b_len, null when no frame is needed), one wave a range.
+hipError_t launch_seek_results(const SeekRead& A, const uint64_t* d_off, const int32_t* b_status,
+                               const uint64_t* b_len, hipStream_t s);
+
 constexpr int N_KERNELS = 6;
 // mode-2 launch groups (LaunchArgs::dom_events: events 2g, 2g + 1)
 constexpr int N_DOM = 5;

@@ -9,7 +9,8 @@ Module map (reference -> here):
   decoders/, literals.rs, sequences.rs -> HIP kernels behind the C ABI (include/zd.h)
 Batch API (the hot path): batch.decompress / batch.Plan; batch.Batch for
 scattered device chunks with per-chunk buffers and statuses; batch.chunk_sizes /
-Batch.packed / batch.decompress_tensors when the decoded sizes are not known.
+Batch.packed / batch.decompress_tensors when the decoded sizes are not known;
+seekable.SeekableArchive for byte ranges of a seekable archive on the device.
 """
 from . import _lib
 from ._lib import ZdError
@@ -19,8 +20,9 @@ from .block import Block
 from .decoding_context import DecodingContext
 from .batch import (Batch, Dictionary, DictionarySet, Plan, chunk_sizes, decode_tensors, decompress,
                     decompress_tensors, frames_index)
+from .seekable import SeekableArchive, SeekReader
 
 __all__ = ["ZdError", "ForwardByteParser", "Frame", "FrameIterator", "Header", "Skippable", "ZStandard",
            "MAX_WIN_SIZE", "Block", "DecodingContext", "Batch", "Dictionary", "DictionarySet",
            "Plan", "chunk_sizes", "decode_tensors", "decompress", "decompress_tensors",
-           "frames_index"]
+           "frames_index", "SeekableArchive", "SeekReader"]

@@ -2,6 +2,7 @@
 
     python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]... [--verify] [--long]
     python -m zstd_decompressor FILE --patch-from OLD -o FILE [--long]
+    python -m zstd_decompressor FILE --range OFF:LEN [-o FILE] [--verify] [--long]
 
 Decodes every frame of FILE on the GPU (the HIP pipeline behind zd_decompress)
 and writes the concatenated output to stdout or --output.  As in the
@@ -28,6 +29,11 @@ Frame_Content_Size is at least 2 MiB (16 blocks of 128 KiB, the block count
 from which a plain plan sends a frame to the block-parallel executor) is
 decoded block-parallel (F_BLOCK_PARALLEL); a smaller one, or one without a
 Frame_Content_Size, on the streaming executor.
+--range OFF:LEN reads content bytes [OFF, OFF + LEN) of FILE, a zstd seekable
+archive (a multi-frame file that ends with a seek table), decoding only the
+entries the range touches; the range is clamped to the content's end and
+written as bytes.  A file without a seek table is an error message and exit
+status 1.  Not together with -D or --patch-from.
 --long accepts frames whose Window_Size is up to 2 GiB (F_LONG_WINDOW; the
 default is the reference's 8 MiB limit): what `zstd --long` and `zstd
 --patch-from` write for inputs past 8 MiB.
@@ -86,7 +92,42 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--long", dest="long_window", action="store_true",
                     help="accept frames whose Window_Size is up to 2 GiB (default: 8 MiB, the reference's limit), "
                          "as written by zstd --long and by --patch-from on large files (not in the reference)")
+    ap.add_argument("--range", dest="byte_range", metavar="OFF:LEN",
+                    help="read LEN content bytes from offset OFF of a zstd seekable archive, decoding only the "
+                         "entries they lie in (not in the reference; not together with -D or --patch-from)")
     return ap
+
+
+def _range(a, data: bytes) -> int:
+    """--range OFF:LEN: one range of a seekable archive, written as bytes."""
+    from .seekable import SeekableArchive
+    try:
+        off, length = (int(v, 0) for v in a.byte_range.split(":"))
+        if off < 0 or length < 0:
+            raise ValueError
+    except ValueError:
+        print("Error: --range takes OFF:LEN, two non-negative integers", file=sys.stderr)
+        return 2
+    try:
+        arc = SeekableArchive(data)
+    except _lib.ZdError as e:
+        print(f"Error: not a seekable archive: {e.name}", file=sys.stderr)
+        return 1
+    flags = (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0)
+    try:
+        out = bytes(arc.read(off, length, flags=flags).cpu().numpy().tobytes())
+    except _lib.ZdError as e:
+        print(f"Error: {e.name}", file=sys.stderr)
+        return 1
+    finally:
+        arc.close()
+    if a.output:
+        with open(a.output, "wb") as fo:
+            fo.write(out)
+    else:
+        sys.stdout.buffer.write(out)
+        sys.stdout.buffer.flush()
+    return 0
 
 
 def _patch(a, data: bytes) -> int:
@@ -146,10 +187,16 @@ def main(argv=None) -> int:
     if a.info:
         return _info(data)
     if a.patch_from:
-        if a.dictionary:
-            print("Error: --patch-from and -D exclude one another", file=sys.stderr)
+        if a.dictionary or a.byte_range is not None:
+            print("Error: --patch-from and -D / --range exclude one another" if a.byte_range is not None else
+                  "Error: --patch-from and -D exclude one another", file=sys.stderr)
             return 2
         return _patch(a, data)
+    if a.byte_range is not None:
+        if a.dictionary:
+            print("Error: --range and -D exclude one another", file=sys.stderr)
+            return 2
+        return _range(a, data)
     import torch
     try:
         dictionary = _dictionary(a.dictionary) if a.dictionary else None

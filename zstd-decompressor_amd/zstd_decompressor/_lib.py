@@ -73,6 +73,18 @@ class BatchInfo2(BatchInfoEx):
     _fields_ = [("k4j_chunks", C.c_uint64)]
 
 
+class SeekableInfo(C.Structure):
+    """zd_seekable_info"""
+    _fields_ = [("nframes", C.c_uint64), ("content_bytes", C.c_uint64), ("compressed_bytes", C.c_uint64),
+                ("table_bytes", C.c_uint64), ("has_checksums", C.c_uint32), ("max_frame_content", C.c_uint32)]
+
+
+class SeekReadInfo(C.Structure):
+    """zd_seek_read_info"""
+    _fields_ = [("nranges", C.c_uint64), ("frames_decoded", C.c_uint64), ("frames_in_place", C.c_uint64),
+                ("staged_bytes", C.c_uint64), ("copy_pieces", C.c_uint64), ("batch", BatchInfo2)]
+
+
 COMM_ID_BYTES = 128
 
 # every entry point declared in include/zd.h: name -> (restype, argtypes)
@@ -139,6 +151,18 @@ SIGNATURES = {
                                    C.POINTER(C.c_uint64)]),
     "zd_batch_checksums": (C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "zd_batch_destroy": (None, [_vp]),
+    "zd_seekable_open_device": (C.c_int, [_vp, _sz, _vp, C.POINTER(_vp)]),
+    "zd_seekable_info_get": (C.c_int, [_vp, C.POINTER(SeekableInfo)]),
+    "zd_seekable_table": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "zd_seekable_close": (None, [_vp]),
+    "zd_seekable_read_create": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "zd_seek_read_decode_async": (C.c_int, [_vp, _vp]),
+    "zd_seek_read_finish_async": (C.c_int, [_vp, _vp]),
+    "zd_seek_read_device_results": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "zd_seek_read_results": (C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _sz,
+                                       C.POINTER(C.c_uint64)]),
+    "zd_seek_read_info_get": (C.c_int, [_vp, C.POINTER(SeekReadInfo)]),
+    "zd_seek_read_destroy": (None, [_vp]),
     "zd_context_new": (C.c_int, [C.c_uint64, C.POINTER(_vp)]),
     "zd_context_free": (None, [_vp]),
     "zd_block_decode": (C.c_int, [_vp, _vp, _sz, _szp, C.POINTER(C.c_int)]),
@@ -265,6 +289,7 @@ UNRECOGNIZED_MAGIC, FRAME_RESERVED_SET, MISSING_CHECKSUM, WINDOW_SIZE_TOO_BIG = 
 REF_PANIC, OUT_OF_DOMAIN, DST_TOO_SMALL, INVALID_ARG, HIP, NO_MEMORY, NOT_DECODED = -90, -91, -92, -93, -94, -95, -96
 DICT_CORRUPTED, DICT_MISMATCH = -98, -99
 CHECKSUM_WRONG = -100  # F_VERIFY_CHECKSUM: the frame decoded, its bytes do not hash to its Content_Checksum
+SEEK_TABLE = -101      # a seekable archive's table contradicts itself or the archive; a frame of another length
 DICT_SET_MAX = 4096    # ZD_DICT_SET_MAX
 CHAIN_MAX_DEPTH = 255  # ZD_CHAIN_MAX_DEPTH: in-batch ancestors a chunk of a chain batch may have
 F_SKIPPABLE = 1
