@@ -1,4 +1,7 @@
-// zd_launch.h — host-side entry points of the gfx950 kernels (zd_kernels.hip).
+// zd_launch.h — host-side entry points of the gfx950 kernels: launch_pipeline,
+// launch_reset, launch_dict_tables and launch_compact in zd_pipeline.hip, the
+// seekable layer's in zd_seek.hip, the others beside their kernels in
+// zd_kernels.hip (the one translation unit, which includes the two files).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
