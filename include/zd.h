@@ -1000,8 +1000,9 @@ void zd_batch_destroy(zd_batch* batch);
 /* An entry is treated as a batch chunk: one zstd frame with any number */
 /* of skippable frames around it; an entry of two zstd frames is that   */
 /* chunk's ZD_E_OUT_OF_DOMAIN, as in any batch (a documented limit).    */
-/* Limits: no dictionary, prefix or chain reads; the table's own        */
-/* per-entry checksums are exposed, not verified; a read's destinations */
+/* The table's per-entry checksums are verified inside the launch by a  */
+/* read made with ZD_SEEK_VERIFY_TABLE (zd_seekable_read_create_ex).    */
+/* Limits: no dictionary, prefix or chain reads; a read's destinations  */
 /* cannot be re-pointed; the ranges come as device arrays only; nothing */
 /* of this in zd_plan_*, the sharded calls or zd_context.               */
 /* ------------------------------------------------------------------ */
@@ -1079,6 +1080,46 @@ void zd_seekable_close(zd_seekable* z);
 int  zd_seekable_read_create(zd_seekable* z, const uint64_t* d_off, const uint64_t* d_len,
                              void* const* d_dst, size_t nranges, uint32_t flags,
                              void* stream, zd_seek_read** out);
+/* A read's own options (read_flags; not plan flags, which go to the inner
+ * batch).  ZD_SEEK_VERIFY_TABLE: every launch compares the seek table's
+ * Checksum -- the low 32 bits of XXH64, seed 0, of the entry's decoded bytes,
+ * the archive format's integrity mechanism -- of every needed entry, as zstd's
+ * own seekable reader does on every read. */
+#define ZD_SEEK_VERIFY_TABLE 1u
+/* zd_seekable_read_create with a read option word; read_flags 0 is that call.
+ * Two more ZD_E_INVALID_ARG cases for the whole call, both before any HIP call
+ * of this function: unknown read_flags bits; ZD_SEEK_VERIFY_TABLE on an
+ * archive whose table carries no checksums (zd_seekable_info.has_checksums 0:
+ * a caller who asks for verification never silently gets none).  No host wait
+ * is added to the creation.
+ * A verified read's zd_seek_read_decode_async queues the inner batch's decode,
+ * zd_k_seek_verify, zd_k_seek_finish and the result pass; zd_seek_read_finish_
+ * async and the re-run inside zd_seek_read_results include the verify pass.
+ * An entry is COMPARED when it is a needed entry whose chunk ended ZD_OK with
+ * a decoded length equal to its Decompressed_Size: its bytes are hashed where
+ * they were decoded (the destination or the staging buffer, at any alignment,
+ * never a byte outside them), once per launch however many ranges touch it.
+ * Every other entry is never read (verdict -1); entries of no content bytes
+ * are never decoded and never compared.  With ZD_F_VERIFY_CHECKSUM in flags,
+ * an entry whose frame's own Content_Checksum the inner batch verified
+ * (d_ok[k] == 1 in zd_batch_device_checksums) is compared by the low 32 bits
+ * of that digest and not read again.
+ * Range status: among the frames "that did not end ZD_OK" now also counts an
+ * entry that was compared and differs, as ZD_E_CHECKSUM_WRONG; the range's
+ * status is still that of the lowest-numbered such frame, and ZD_E_SEEK_TABLE
+ * what it gets when no frame failed but a length differs. */
+int  zd_seekable_read_create_ex(zd_seekable* z, const uint64_t* d_off, const uint64_t* d_len,
+                                void* const* d_dst, size_t nranges, uint32_t flags,
+                                uint32_t read_flags, void* stream, zd_seek_read** out);
+/* A verified read's per-entry verdicts, device arrays the read owns (allocated
+ * at creation), *n = frames_decoded entries each, indexed by the inner batch's
+ * chunk: d_entry[k] the entry's index in the table, d_ok[k] 1 (matches) / 0
+ * (differs) / -1 (not compared), d_hash32[k] the computed low 32 bits, 0 when
+ * d_ok[k] is -1.  Valid behind the work a launch queued; a loader learns from
+ * them which entry to fetch again.  A read made without ZD_SEEK_VERIFY_TABLE:
+ * NULL arrays, *n = 0.  Any pointer may be NULL. */
+int  zd_seek_read_device_verdicts(const zd_seek_read* r, const uint32_t** d_entry, const int8_t** d_ok,
+                                  const uint32_t** d_hash32, uint64_t* n);
 /* Queues, in this order: the inner batch's decode; zd_k_seek_finish, which
  * copies the staged frames' wanted parts to the ranges' destinations (the
  * grid runs over 32 KiB pieces of the destinations; in-place frames are
@@ -1088,9 +1129,12 @@ int  zd_seekable_read_create(zd_seekable* z, const uint64_t* d_off, const uint64
  * with every frame ZD_OK but one whose decoded length differs from its
  * Decompressed_Size, ZD_E_SEEK_TABLE; else ZD_OK.  Its length is the clamped
  * length, or 0 on failure; a failed range's destination bytes are unspecified.
+ * A ZD_SEEK_VERIFY_TABLE read queues zd_k_seek_verify between the decode and
+ * zd_k_seek_finish (zd_seekable_read_create_ex).
  * No allocation, no host synchronisation: capturable, and may be called again. */
 int  zd_seek_read_decode_async(zd_seek_read* r, void* stream);
-/* The finish and result passes alone, behind whatever `stream` holds: what
+/* The finish and result passes alone (a verified read: the verify pass in
+ * front of them), behind whatever `stream` holds: what
  * zd_seek_read_results runs after the inner batch's own results, for a caller
  * that reads the inner batch's state itself, and what a timing run puts between
  * two events.  ZD_E_INVALID_ARG before the first zd_seek_read_decode_async. */
@@ -1112,6 +1156,16 @@ typedef struct zd_seek_read_info {
   zd_batch_info2 batch;        /* the inner batch (zeroed when no frame is needed) */
 } zd_seek_read_info;
 int  zd_seek_read_info_get(const zd_seek_read* r, zd_seek_read_info* info);
+/* What zd_seek_read_info_get_sized writes behind zd_seek_read_info when the
+ * caller's size covers it. */
+typedef struct zd_seek_read_info2 {
+  zd_seek_read_info info;
+  uint64_t read_flags;         /* the read's option word (ZD_SEEK_VERIFY_TABLE) */
+  uint64_t verify_entries;     /* zd_k_seek_verify's entries: frames_decoded with the option, else 0 */
+} zd_seek_read_info2;
+/* The first `bytes` bytes of zd_seek_read_info2 (as zd_batch_info_get_sized);
+ * fewer than sizeof(zd_seek_read_info) is ZD_E_INVALID_ARG. */
+int  zd_seek_read_info_get_sized(const zd_seek_read* r, zd_seek_read_info* info, size_t bytes);
 void zd_seek_read_destroy(zd_seek_read* r);
 
 /* ------------------------------------------------------------------ */

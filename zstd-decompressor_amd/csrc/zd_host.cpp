@@ -3414,6 +3414,12 @@ struct zd_seek_read {
   uint64_t npieces = 0;
   bool launched = false;
   zd_seek_read_info info{};
+  // a ZD_SEEK_VERIFY_TABLE read (else all null / 0): one allocation made at creation, frames_decoded entries each
+  uint32_t read_flags = 0;
+  uint8_t* d_vmem = nullptr;             // v_addr | v_entry | v_hash32 | v_ok
+  uint64_t* v_addr = nullptr;            // where the chunk decodes to (the chunk table itself is freed after creation)
+  uint32_t *v_entry = nullptr, *v_hash32 = nullptr;
+  int8_t* v_ok = nullptr;
 };
 
 extern "C" {
@@ -3490,21 +3496,32 @@ void zd_seek_read_destroy(zd_seek_read* r) {
   if (r->B) zd_batch_destroy(r->B);
   ws_release(r->d_stage, r->stage_alloc, r->dev);
   if (r->d_mem) (void)hipFree(r->d_mem);
+  if (r->d_vmem) (void)hipFree(r->d_vmem);
   delete r;
 }
 
 int zd_seekable_read_create(zd_seekable* z, const uint64_t* d_off, const uint64_t* d_len, void* const* d_dst,
                             size_t nranges, uint32_t flags, void* stream, zd_seek_read** out) {
+  return zd_seekable_read_create_ex(z, d_off, d_len, d_dst, nranges, flags, 0, stream, out);
+}
+
+int zd_seekable_read_create_ex(zd_seekable* z, const uint64_t* d_off, const uint64_t* d_len, void* const* d_dst,
+                               size_t nranges, uint32_t flags, uint32_t read_flags, void* stream,
+                               zd_seek_read** out) {
   // ---- argument checks: no HIP call before they are done (z is looked at last) ----
-  if (!out || (flags & ZD_F_SKIPPABLE) || (flags & ~(SEEK_READ_FLAGS | ZD_F_SKIPPABLE)) || nranges >= (1ull << 31))
+  if (!out || (flags & ZD_F_SKIPPABLE) || (flags & ~(SEEK_READ_FLAGS | ZD_F_SKIPPABLE)) || nranges >= (1ull << 31) ||
+      (read_flags & ~ZD_SEEK_VERIFY_TABLE))
     return ZD_E_INVALID_ARG;
   if (nranges && (!d_off || !d_len || !d_dst)) return ZD_E_INVALID_ARG;
   if (!z || !z->p) return ZD_E_INVALID_ARG;
+  const bool verify = (read_flags & ZD_SEEK_VERIFY_TABLE) != 0;
+  if (verify && !z->p->checksum) return ZD_E_INVALID_ARG;        // (nothing to verify with: never silently none)
   struct DropRead { void operator()(zd_seek_read* r) const { zd_seek_read_destroy(r); } };
   std::unique_ptr<zd_seek_read, DropRead> hold(new (std::nothrow) zd_seek_read());
   zd_seek_read* r = hold.get();
   if (!r) return ZD_E_NO_MEMORY;
   r->a = z->p;
+  r->read_flags = read_flags;
   r->info.nranges = nranges;
   if (!nranges) { *out = hold.release(); return ZD_OK; }
   const SeekData& D = *r->a;
@@ -3554,8 +3571,19 @@ int zd_seekable_read_create(zd_seekable* z, const uint64_t* d_off, const uint64_
   uint64_t* cols = nullptr;
   HIPCHK(hipMalloc(&cols, 4 * 8 * needed));
   std::unique_ptr<void, Free> cols_mem(cols);
+  if (verify) {
+    // the verdicts and what zd_k_seek_verify needs of every chunk; before the first launch: not compared (-1, 0)
+    const uint64_t o_entry = 8 * needed, o_hash = o_entry + up16(4 * needed), o_ok = o_hash + up16(4 * needed);
+    HIPCHK(hipMalloc(&r->d_vmem, o_ok + needed));
+    HIPCHK(hipMemsetAsync(r->d_vmem, 0, o_ok, s));
+    HIPCHK(hipMemsetAsync(r->d_vmem + o_ok, 0xFF, needed, s));
+    r->v_addr = (uint64_t*)r->d_vmem;
+    r->v_entry = (uint32_t*)(r->d_vmem + o_entry);
+    r->v_hash32 = (uint32_t*)(r->d_vmem + o_hash);
+    r->v_ok = (int8_t*)(r->d_vmem + o_ok);
+  }
   HIPCHK(launch_seek_chunks(A, D.d_archive, D.c_off, D.d_off, r->d_stage, cols, cols + needed, cols + 2 * needed,
-                            cols + 3 * needed, s));
+                            cols + 3 * needed, r->v_entry, r->v_addr, s));
   BatchSpec S{(const void* const*)cols, cols + needed, (void* const*)(cols + 2 * needed), cols + 3 * needed};
   S.on_device = true; S.n = (size_t)needed; S.flags = flags; S.stream = s;
   if (int e = batch_create(S, &r->B)) return e;
@@ -3564,13 +3592,21 @@ int zd_seekable_read_create(zd_seekable* z, const uint64_t* d_off, const uint64_
   return ZD_OK;
 }
 
-// the finish and result passes, behind the inner batch's work on s
+// the verify (a ZD_SEEK_VERIFY_TABLE read), finish and result passes, behind the inner batch's work on s
 static int seek_passes(zd_seek_read* r, hipStream_t s) {
   const int32_t* b_status = nullptr;
   const uint64_t* b_len = nullptr;
   if (r->B) (void)zd_batch_device_results(r->B, &b_status, &b_len);
+  if (r->v_ok && r->B) {
+    // (a ZD_F_VERIFY_CHECKSUM read: the frames the inner batch hashed are not hashed again)
+    const uint64_t* b_hash = nullptr;
+    const int8_t* b_ok = nullptr;
+    if (zd_batch_device_checksums(r->B, &b_hash, &b_ok) != ZD_OK || !b_hash || !b_ok) b_hash = nullptr, b_ok = nullptr;
+    HIPCHK(launch_seek_verify(r->v_entry, r->v_addr, (uint32_t)r->info.frames_decoded, r->a->d_off, r->a->checksum,
+                              b_status, b_len, b_hash, b_ok, r->v_ok, r->v_hash32, s));
+  }
   HIPCHK(launch_seek_finish(r->A, r->a->d_off, r->d_stage, r->npieces, s));
-  HIPCHK(launch_seek_results(r->A, r->a->d_off, b_status, b_len, s));
+  HIPCHK(launch_seek_results(r->A, r->a->d_off, b_status, b_len, r->v_ok, s));
   return 0;
 }
 
@@ -3627,6 +3663,26 @@ int zd_seek_read_results(zd_seek_read* r, void* stream, int32_t* status, uint64_
 int zd_seek_read_info_get(const zd_seek_read* r, zd_seek_read_info* info) {
   if (!r || !info) return ZD_E_INVALID_ARG;
   *info = r->info;
+  return ZD_OK;
+}
+
+int zd_seek_read_info_get_sized(const zd_seek_read* r, zd_seek_read_info* info, size_t bytes) {
+  if (!r || !info || bytes < sizeof(zd_seek_read_info)) return ZD_E_INVALID_ARG;
+  zd_seek_read_info2 I{};
+  I.info = r->info;
+  I.read_flags = r->read_flags;
+  I.verify_entries = r->v_ok ? r->info.frames_decoded : 0;
+  memcpy(info, &I, std::min(bytes, sizeof I));
+  return ZD_OK;
+}
+
+int zd_seek_read_device_verdicts(const zd_seek_read* r, const uint32_t** d_entry, const int8_t** d_ok,
+                                 const uint32_t** d_hash32, uint64_t* n) {
+  if (!r) return ZD_E_INVALID_ARG;
+  if (d_entry) *d_entry = r->v_entry;
+  if (d_ok) *d_ok = r->v_ok;
+  if (d_hash32) *d_hash32 = r->v_hash32;
+  if (n) *n = r->v_ok ? r->info.frames_decoded : 0;
   return ZD_OK;
 }
 

@@ -272,18 +272,33 @@ struct SeekRead {
 hipError_t launch_seek_layout(const uint64_t* off, const uint64_t* len, const uint64_t* dst, const uint64_t* d_off,
                               const SeekRead& A, uint64_t* tot, uint64_t* res, hipStream_t s);
 // zd_k_seek_chunks: the inner batch's chunk table, four columns of `needed`
-// entries (src, size, dst, cap), one wave a range.
+// entries (src, size, dst, cap), one wave a range.  v_entry / v_addr (both or
+// neither; `needed` entries): the chunk's entry in the table and the address
+// it decodes to, kept by a verified read.
 hipError_t launch_seek_chunks(const SeekRead& A, const uint8_t* archive, const uint64_t* c_off, const uint64_t* d_off,
                               uint8_t* staging, uint64_t* col_src, uint64_t* col_size, uint64_t* col_dst,
-                              uint64_t* col_cap, hipStream_t s);
+                              uint64_t* col_cap, uint32_t* v_entry, uint64_t* v_addr, hipStream_t s);
+// zd_k_seek_verify (a ZD_SEEK_VERIFY_TABLE read, behind the inner batch's
+// decode): chunk k of n, entry v_entry[k] decoded at v_addr[k], is compared when
+// it ended ZD_OK (b_status) with its Decompressed_Size (b_len): ok[k] = 1 / 0
+// and hash32[k] = the low 32 bits of XXH64 of its bytes; else ok[k] = -1,
+// hash32[k] = 0 and nothing of it is read.  b_hash / b_ok: the inner batch's
+// zd_batch_device_checksums arrays or null; a chunk with b_ok[k] == 1 is
+// compared by b_hash[k] and not read again.  Four lanes a chunk.
+hipError_t launch_seek_verify(const uint32_t* v_entry, const uint64_t* v_addr, uint32_t n, const uint64_t* d_off,
+                              const uint32_t* checksum, const int32_t* b_status, const uint64_t* b_len,
+                              const uint64_t* b_hash, const int8_t* b_ok, int8_t* ok, uint32_t* hash32,
+                              hipStream_t s);
 // zd_k_seek_finish: the staged frames' wanted parts to the destinations, one
 // workgroup a 32 KiB piece of a range.
 hipError_t launch_seek_finish(const SeekRead& A, const uint64_t* d_off, const uint8_t* staging, uint64_t npieces,
                               hipStream_t s);
 // zd_k_seek_results: the ranges' statuses and lengths from the inner batch's
-// (b_status / b_len, null when no frame is needed), one wave a range.
+// (b_status / b_len, null when no frame is needed), one wave a range.  v_ok:
+// zd_k_seek_verify's verdicts, or null (a read without ZD_SEEK_VERIFY_TABLE);
+// a chunk of verdict 0 counts as ZD_E_CHECKSUM_WRONG.
 hipError_t launch_seek_results(const SeekRead& A, const uint64_t* d_off, const int32_t* b_status,
-                               const uint64_t* b_len, hipStream_t s);
+                               const uint64_t* b_len, const int8_t* v_ok, hipStream_t s);
 
 constexpr int N_KERNELS = 6;
 // mode-2 launch groups (LaunchArgs::dom_events: events 2g, 2g + 1)

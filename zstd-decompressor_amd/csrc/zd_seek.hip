@@ -18,6 +18,9 @@
 //   zd_k_seek_totals  the words that come back to the host
 //   zd_k_seek_chunks  one wave a range: the inner batch's four columns
 // A launch (zd_seek_read_decode_async), behind the inner batch's decode:
+//   zd_k_seek_verify  (a ZD_SEEK_VERIFY_TABLE read) four lanes a needed entry:
+//                     its bytes hashed where they were decoded, the low 32
+//                     bits compared with the table's Checksum
 //   zd_k_seek_finish  one workgroup a 32 KiB piece of a range's destination
 //   zd_k_seek_results one wave a range
 #include <hip/hip_runtime.h>
@@ -172,11 +175,13 @@ hipError_t launch_seek_layout(const uint64_t* off, const uint64_t* len, const ui
 // when the frame is in place (then this range is the only one that touches
 // it) and at its staging offset otherwise (every range that touches a staged
 // frame writes the same four words).  Capacity: the table's Decompressed_Size.
+// v_entry / v_addr (a verified read's, else null): the chunk's entry and the
+// address it decodes to, which zd_k_seek_verify reads at every launch.
 __global__ __launch_bounds__(256) void zd_k_seek_chunks(SeekRead A, const uint8_t* archive,
                                                         const uint64_t* __restrict__ c_off,
                                                         const uint64_t* __restrict__ d_off, uint8_t* staging,
                                                         uint64_t* col_src, uint64_t* col_size, uint64_t* col_dst,
-                                                        uint64_t* col_cap) {
+                                                        uint64_t* col_cap, uint32_t* v_entry, uint64_t* v_addr) {
   const uint32_t i = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x & 63;
   if (i >= A.R) return;
   const uint64_t l = A.len[i];
@@ -192,17 +197,137 @@ __global__ __launch_bounds__(256) void zd_k_seek_chunks(SeekRead A, const uint8_
     const bool inplace = seek_in_place(A.cover[f], A.partial[f]);
     col_src[k] = (uint64_t)(uintptr_t)archive + c_off[f];
     col_size[k] = c_off[f + 1] - c_off[f];
-    col_dst[k] = inplace ? d + at : (uint64_t)(uintptr_t)staging + A.soff[f];
+    const uint64_t to = inplace ? d + at : (uint64_t)(uintptr_t)staging + A.soff[f];
+    col_dst[k] = to;
     col_cap[k] = fb - fa;
+    if (v_entry) v_entry[k] = (uint32_t)f;
+    if (v_addr) v_addr[k] = to;
   }
 }
 
 hipError_t launch_seek_chunks(const SeekRead& A, const uint8_t* archive, const uint64_t* c_off, const uint64_t* d_off,
                               uint8_t* staging, uint64_t* col_src, uint64_t* col_size, uint64_t* col_dst,
-                              uint64_t* col_cap, hipStream_t s) {
+                              uint64_t* col_cap, uint32_t* v_entry, uint64_t* v_addr, hipStream_t s) {
   if (!A.R || !A.F) return hipSuccess;
   hipLaunchKernelGGL(zd_k_seek_chunks, dim3((A.R + 3) / 4), dim3(256), 0, s, A, archive, c_off, d_off, staging,
-                     col_src, col_size, col_dst, col_cap);
+                     col_src, col_size, col_dst, col_cap, v_entry, v_addr);
+  return hipGetLastError();
+}
+
+// zd_k_seek_verify (a ZD_SEEK_VERIFY_TABLE read, between the inner batch's
+// decode and zd_k_seek_finish): the table's Checksum, the low 32 bits of XXH64
+// of the entry's decoded bytes, compared for every chunk that ended ZD_OK with
+// its entry's Decompressed_Size.  zd_k_verify's layout and its 32-byte-row body
+// (seek_xx_lines): four lanes a chunk, lane `sub` accumulator `sub`, 16 chunks a
+// wave; always the rows, entries being KiB to MiB and few.  The bytes are read
+// where the chunk decoded them, v_addr[k]: a range's destination for an entry in
+// place, the staging buffer otherwise, at whatever alignment that has, and every
+// load lies inside [p, p + Decompressed_Size).  A chunk is an entry, so an entry
+// is hashed once however many ranges touch it.  b_ok / b_hash (a
+// ZD_F_VERIFY_CHECKSUM read's, else null): a chunk whose frame's own
+// Content_Checksum the inner batch verified (b_ok[k] == 1) was hashed there; the
+// low half of that digest is compared and the bytes are not read again.  Every
+// other chunk is not read: ok -1, hash32 0.  Writes ok and hash32, nothing else.
+//
+// seek_xx_lines is a copy of the LINES body of zd_k_verify (zd_kernels.hip), not
+// a function both call: with the body moved into one __device__ function,
+// zd_k_verify<true> compiled to other code for gfx950 (986 against 1,026 lines
+// of assembly), so that kernel stays as it was.  The whole 128-byte lines of
+// [p, p + 32 nst) into accumulator `sub` of the quad: a line is four 32-byte
+// rows of two ldg16, quad_transpose64 hands lane k word k of the four stripes,
+// VF_U lines go a trip with the next trip's loads issued before this trip's
+// rounds.  Returns the stripes eaten (four a line).
+__device__ inline uint64_t seek_xx_lines(const uint8_t* p, uint64_t nst, int sub, uint64_t& v) {
+  const uint64_t nl = nst / 4;
+  auto row = [&](uint64_t line, u32x4& a, u32x4& b) {
+    const uint8_t* q = p + 128 * line + 32 * sub;
+    a = ldg16(q);
+    b = ldg16(q + 16);
+  };
+  auto eat = [&](const u32x4& a, const u32x4& b) {
+    uint64_t w[4] = {(uint64_t)a.x | ((uint64_t)a.y << 32), (uint64_t)a.z | ((uint64_t)a.w << 32),
+                     (uint64_t)b.x | ((uint64_t)b.y << 32), (uint64_t)b.z | ((uint64_t)b.w << 32)};
+    quad_transpose64(w, sub);
+    v = xx_round(xx_round(xx_round(xx_round(v, w[0]), w[1]), w[2]), w[3]);
+  };
+  u32x4 ca[VF_U] = {}, cb[VF_U] = {};
+  uint64_t t = 0;
+  if (VF_U <= nl) {
+#pragma unroll
+    for (int k = 0; k < VF_U; k++) row(k, ca[k], cb[k]);
+  }
+  while (t + VF_U <= nl) {
+    u32x4 na[VF_U], nb[VF_U];
+#pragma unroll
+    for (int k = 0; k < VF_U; k++) { na[k] = ca[k]; nb[k] = cb[k]; }
+    if (t + 2 * VF_U <= nl) {                       // the next trip's lines, before this trip's rounds
+#pragma unroll
+      for (int k = 0; k < VF_U; k++) row(t + VF_U + k, na[k], nb[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < VF_U; k++) eat(ca[k], cb[k]);
+#pragma unroll
+    for (int k = 0; k < VF_U; k++) { ca[k] = na[k]; cb[k] = nb[k]; }
+    t += VF_U;
+  }
+  for (; t < nl; t++) {
+    u32x4 a, b;
+    row(t, a, b);
+    eat(a, b);
+  }
+  return 4 * nl;
+}
+
+__global__ __launch_bounds__(64) void zd_k_seek_verify(const uint32_t* __restrict__ v_entry,
+                                                       const uint64_t* __restrict__ v_addr, uint32_t n,
+                                                       const uint64_t* __restrict__ d_off,
+                                                       const uint32_t* __restrict__ checksum,
+                                                       const int32_t* __restrict__ b_status,
+                                                       const uint64_t* __restrict__ b_len,
+                                                       const uint64_t* __restrict__ b_hash,
+                                                       const int8_t* __restrict__ b_ok, int8_t* ok, uint32_t* hash32) {
+  const int lane = threadIdx.x, sub = lane & 3;
+  const uint32_t k = blockIdx.x * 16 + (lane >> 2);
+  uint64_t L = 0, size = 0;
+  const uint8_t* p = nullptr;
+  uint32_t want = 0, have = 0;
+  bool act = false, hashed = false;
+  if (k < n) {
+    const uint32_t f = v_entry[k];
+    size = d_off[f + 1] - d_off[f];
+    act = b_status[k] == ZD_OK && b_len[k] == size;
+    if (act) {
+      want = checksum[f];
+      hashed = b_ok && b_ok[k] == 1;
+      if (hashed) {
+        have = (uint32_t)b_hash[k];
+      } else {
+        L = size;
+        p = (const uint8_t*)(uintptr_t)v_addr[k];
+      }
+    }
+  }
+  const uint64_t nst = L / 32;
+  uint64_t v = xx_acc_init(sub);
+  uint64_t s = seek_xx_lines(p, nst, sub, v);
+  for (; s < nst; s++) v = xx_round(v, *(g_cu64a1*)(p + 32 * s + 8 * sub));
+  // (the lanes have reconverged: the four accumulators into every lane of the quad)
+  const uint64_t acc[4] = {qdpp64<0x00>(v), qdpp64<0x55>(v), qdpp64<0xAA>(v), qdpp64<0xFF>(v)};
+  if (k < n && sub == 0) {
+    if (act && !hashed) have = (uint32_t)xx_finish(L, acc, p + 32 * nst, (uint32_t)(L - 32 * nst));
+    ok[k] = act ? (have == want ? 1 : 0) : -1;
+    hash32[k] = act ? have : 0;
+  }
+}
+
+hipError_t launch_seek_verify(const uint32_t* v_entry, const uint64_t* v_addr, uint32_t n, const uint64_t* d_off,
+                              const uint32_t* checksum, const int32_t* b_status, const uint64_t* b_len,
+                              const uint64_t* b_hash, const int8_t* b_ok, int8_t* ok, uint32_t* hash32,
+                              hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (!v_entry || !v_addr || !checksum || !b_status || !b_len || !ok || !hash32) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(zd_k_seek_verify, dim3((n + 15) / 16), dim3(64), 0, s, v_entry, v_addr, n, d_off, checksum,
+                     b_status, b_len, b_hash, b_ok, ok, hash32);
   return hipGetLastError();
 }
 
@@ -260,10 +385,14 @@ hipError_t launch_seek_finish(const SeekRead& A, const uint64_t* d_off, const ui
 // zd_k_seek_results: range i's status is that of the lowest-numbered of its
 // frames whose chunk did not end ZD_OK; with every chunk ZD_OK but one whose
 // decoded length is not the table's Decompressed_Size, ZD_E_SEEK_TABLE.  Its
-// length: the clamped length, or 0 on failure.
+// length: the clamped length, or 0 on failure.  v_ok (zd_k_seek_verify's
+// verdicts, null for a read without ZD_SEEK_VERIFY_TABLE): a frame that was
+// compared and differs (0) counts among the frames that did not end ZD_OK, as
+// ZD_E_CHECKSUM_WRONG.
 __global__ __launch_bounds__(256) void zd_k_seek_results(SeekRead A, const uint64_t* __restrict__ d_off,
                                                          const int32_t* __restrict__ b_status,
-                                                         const uint64_t* __restrict__ b_len) {
+                                                         const uint64_t* __restrict__ b_len,
+                                                         const int8_t* __restrict__ v_ok) {
   const uint32_t i = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x & 63;
   if (i >= A.R) return;
   const uint64_t l = A.len[i];
@@ -280,6 +409,7 @@ __global__ __launch_bounds__(256) void zd_k_seek_results(SeekRead A, const uint6
       const uint64_t k = A.idx[f];
       if (b_status[k]) { if (f < firstbad) firstbad = f; }
       else if (b_len[k] != fb - fa) mismatch = 1;
+      else if (v_ok && v_ok[k] == 0) { if (f < firstbad) firstbad = f; }
     }
   }
   for (int k = 32; k; k >>= 1) {
@@ -290,16 +420,18 @@ __global__ __launch_bounds__(256) void zd_k_seek_results(SeekRead A, const uint6
   if (lane) return;
   int st = ZD_OK;
   if (A.bad[i]) st = ZD_E_INVALID_ARG;
-  else if (firstbad != ~0ull) st = b_status[A.idx[firstbad]];
-  else if (mismatch) st = ZD_E_SEEK_TABLE;
+  else if (firstbad != ~0ull) {
+    st = b_status[A.idx[firstbad]];
+    if (v_ok && !st) st = ZD_E_CHECKSUM_WRONG;     // (its chunk ended ZD_OK: the entry that was compared and differs)
+  } else if (mismatch) st = ZD_E_SEEK_TABLE;
   A.status[i] = st;
   A.out_len[i] = st ? 0 : l;
 }
 
 hipError_t launch_seek_results(const SeekRead& A, const uint64_t* d_off, const int32_t* b_status,
-                               const uint64_t* b_len, hipStream_t s) {
+                               const uint64_t* b_len, const int8_t* v_ok, hipStream_t s) {
   if (!A.R) return hipSuccess;
-  hipLaunchKernelGGL(zd_k_seek_results, dim3((A.R + 3) / 4), dim3(256), 0, s, A, d_off, b_status, b_len);
+  hipLaunchKernelGGL(zd_k_seek_results, dim3((A.R + 3) / 4), dim3(256), 0, s, A, d_off, b_status, b_len, v_ok);
   return hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 
     python -m zstd_decompressor FILE [-i/--info] [-o/--output FILE] [-p/--print-skippable] [-D DICT]... [--verify] [--long]
     python -m zstd_decompressor FILE --patch-from OLD -o FILE [--long]
-    python -m zstd_decompressor FILE --range OFF:LEN [-o FILE] [--verify] [--long]
+    python -m zstd_decompressor FILE --range OFF:LEN [-o FILE] [--verify] [--verify-table] [--long]
+    python -m zstd_decompressor FILE --verify-table [--verify] [--long]
 
 Decodes every frame of FILE on the GPU (the HIP pipeline behind zd_decompress)
 and writes the concatenated output to stdout or --output.  As in the
@@ -34,6 +35,14 @@ archive (a multi-frame file that ends with a seek table), decoding only the
 entries the range touches; the range is clamped to the content's end and
 written as bytes.  A file without a seek table is an error message and exit
 status 1.  Not together with -D or --patch-from.
+--verify-table with --range compares the seek table's checksum of every entry
+the range touches inside the launch: an entry whose decoded bytes do not hash
+to it ends the run with `Error: entry N: ChecksumWrong` (exit status 1), and
+an archive whose table carries no checksums is an error.  --verify-table
+without --range decodes every entry of the archive and compares it (as
+`zstd -t` tests a file): one `Error: entry N: <status>` line per bad entry on
+stderr, exit status 1 when there is one, nothing written.  --verify keeps its
+meaning: the frames' own Content_Checksums.
 --long accepts frames whose Window_Size is up to 2 GiB (F_LONG_WINDOW; the
 default is the reference's 8 MiB limit): what `zstd --long` and `zstd
 --patch-from` write for inputs past 8 MiB.
@@ -95,6 +104,10 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--range", dest="byte_range", metavar="OFF:LEN",
                     help="read LEN content bytes from offset OFF of a zstd seekable archive, decoding only the "
                          "entries they lie in (not in the reference; not together with -D or --patch-from)")
+    ap.add_argument("--verify-table", dest="verify_table", action="store_true",
+                    help="a zstd seekable archive: compare every decoded entry with its checksum in the seek table; "
+                         "with --range the entries the range touches, without it the whole archive (not in the "
+                         "reference)")
     return ap
 
 
@@ -115,9 +128,14 @@ def _range(a, data: bytes) -> int:
         return 1
     flags = (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0)
     try:
-        out = bytes(arc.read(off, length, flags=flags).cpu().numpy().tobytes())
+        out = bytes(arc.read(off, length, flags=flags, verify_table=a.verify_table).cpu().numpy().tobytes())
     except _lib.ZdError as e:
-        print(f"Error: {e.name}", file=sys.stderr)
+        if a.verify_table and e.code == _lib.INVALID_ARG and not arc.has_checksums:
+            print("Error: --verify-table: the seek table carries no checksums", file=sys.stderr)
+        elif getattr(e, "entries", None):
+            print(f"Error: entry {e.entries[0]}: {e.name}", file=sys.stderr)
+        else:
+            print(f"Error: {e.name}", file=sys.stderr)
         return 1
     finally:
         arc.close()
@@ -128,6 +146,28 @@ def _range(a, data: bytes) -> int:
         sys.stdout.buffer.write(out)
         sys.stdout.buffer.flush()
     return 0
+
+
+def _verify_table(a, data: bytes) -> int:
+    """--verify-table without --range: every entry of a seekable archive decoded
+    and compared with the table's Checksum, one line per bad entry."""
+    from .seekable import SeekableArchive
+    try:
+        arc = SeekableArchive(data)
+    except _lib.ZdError as e:
+        print(f"Error: not a seekable archive: {e.name}", file=sys.stderr)
+        return 1
+    try:
+        flags = (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0)
+        entries, statuses = arc.verify_all(flags=flags)
+    except ValueError as e:
+        print(f"Error: --verify-table: {e}", file=sys.stderr)
+        return 1
+    finally:
+        arc.close()
+    for f, st in zip(entries, statuses):
+        print(f"Error: entry {f}: {_lib.status_name(st)}", file=sys.stderr)
+    return 1 if entries else 0
 
 
 def _patch(a, data: bytes) -> int:
@@ -197,6 +237,11 @@ def main(argv=None) -> int:
             print("Error: --range and -D exclude one another", file=sys.stderr)
             return 2
         return _range(a, data)
+    if a.verify_table:
+        if a.dictionary:
+            print("Error: --verify-table and -D exclude one another", file=sys.stderr)
+            return 2
+        return _verify_table(a, data)
     import torch
     try:
         dictionary = _dictionary(a.dictionary) if a.dictionary else None

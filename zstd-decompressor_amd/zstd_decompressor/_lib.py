@@ -85,6 +85,12 @@ class SeekReadInfo(C.Structure):
                 ("staged_bytes", C.c_uint64), ("copy_pieces", C.c_uint64), ("batch", BatchInfo2)]
 
 
+class SeekReadInfo2(SeekReadInfo):
+    """zd_seek_read_info2: what zd_seek_read_info_get_sized writes behind
+    zd_seek_read_info when the caller's size covers it."""
+    _fields_ = [("read_flags", C.c_uint64), ("verify_entries", C.c_uint64)]
+
+
 COMM_ID_BYTES = 128
 
 # every entry point declared in include/zd.h: name -> (restype, argtypes)
@@ -162,6 +168,10 @@ SIGNATURES = {
     "zd_seek_read_results": (C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _sz,
                                        C.POINTER(C.c_uint64)]),
     "zd_seek_read_info_get": (C.c_int, [_vp, C.POINTER(SeekReadInfo)]),
+    "zd_seekable_read_create_ex": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "zd_seek_read_device_verdicts": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                               C.POINTER(C.c_uint64)]),
+    "zd_seek_read_info_get_sized": (C.c_int, [_vp, C.POINTER(SeekReadInfo), _sz]),
     "zd_seek_read_destroy": (None, [_vp]),
     "zd_context_new": (C.c_int, [C.c_uint64, C.POINTER(_vp)]),
     "zd_context_free": (None, [_vp]),
@@ -305,6 +315,7 @@ F_VERIFY_CHECKSUM = 1024  # Content_Checksums verified inside the decode launch 
 F_LONG_WINDOW = 2048   # accept a Window_Size up to 2 GiB (default: the reference's 8 MiB limit)
 F_CHAIN_BLOCK_PARALLEL = 4096  # a chain batch (parents=): frames with a compressed block -> K4J, level by level
 F_AUTO_EXECUTOR = 8192  # a prefix or chain batch: each chunk's executor by rule (include/zd.h ZD_AUTO_*)
+SEEK_VERIFY_TABLE = 1  # zd_seekable_read_create_ex read_flags: the seek table's Checksums verified inside the launch
 SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
 SIZES_LONG_WINDOW = 2048  # zd_chunk_sizes_device: the chunks will be decoded with F_LONG_WINDOW (the same bit)
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)
