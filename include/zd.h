@@ -66,7 +66,8 @@ extern "C" {
 #define ZD_E_MISSING_CHECKSUM              (-64)
 #define ZD_E_WINDOW_SIZE_TOO_BIG           (-66)
 /* Beyond the reference */
-#define ZD_E_REF_PANIC       (-90) /* the reference would panic / not terminate here */
+#define ZD_E_REF_PANIC       (-90) /* the reference would panic / not terminate here; from a
+                                      ZD_F_RFC plan only for input that RFC 8878 forbids as well */
 #define ZD_E_OUT_OF_DOMAIN   (-91) /* input outside the GPU path's parity domain */
 #define ZD_E_DST_TOO_SMALL   (-92)
 #define ZD_E_INVALID_ARG     (-93)
@@ -287,6 +288,41 @@ typedef struct zd_plan zd_plan;
                                         time grows with the frames it takes, the streaming executor's with the
                                         longest frame: 256 deltas of 16 blocks 8.2 ms against 10.4, 1,024 of them
                                         33.1 against 11.4; the plain plans' rule has 16 and 1,024 here) */
+/* Decode frames as RFC 8878 and libzstd have them (opt-in).  The default is the
+ * reference's decoder, its departures from the format included (SURVEY.md §2.1
+ * D1-D9); three of them reject or corrupt frames that libzstd writes.  With this
+ * flag, and only with it:
+ *  - D1: the three-byte Number_of_Sequences is byte1 + (byte2 << 8) + 0x7F00
+ *    (the reference adds 0x7F, and decodes such a block to the wrong bytes);
+ *  - D2: a compressed block with 0 sequences is valid: its literals are its
+ *    output, and it leaves the repeat offsets, the previous FSE tables and the
+ *    previous Huffman tree as they were (the reference fails the frame with
+ *    ZD_E_NO_PREVIOUS_DECODER or ZD_E_EMPTY_INPUT_DATA);
+ *  - D3: Huffman weights follow RFC 8878 4.2.1.1: Max_Number_of_Bits is
+ *    highbit(sum of 2^(w-1)) + 1, the last weight fills the sum up to
+ *    2^Max_Number_of_Bits, and what is left to fill must be a power of two,
+ *    else ZD_E_CORRUPTED_TABLE (the reference is ZD_E_REF_PANIC on a sum that is
+ *    a power of two, and truncates the rest to 8 bits);
+ *  - D8: Regenerated_Size is enforced: Huffman streams that do not decode to
+ *    exactly their shares of it, an empty stream among the four, are
+ *    ZD_E_CORRUPTED_STREAMS_SIZE (the reference concatenates what the streams
+ *    give); stream sizes are not truncated to 16 bits;
+ *  - an empty Raw literals section is accepted in every kind of plan.
+ * Everything else is as without the flag: the window limit (ZD_F_LONG_WINDOW is
+ * its own flag), no window check on offsets, checksums (ZD_F_VERIFY_CHECKSUM),
+ * routing and executors.  ZD_E_REF_PANIC may still come out of such a plan, but
+ * only for input that RFC 8878 forbids too (an offset that evaluates to 0, a
+ * corrupt FSE description, Huffman weights that overflow 32 bits).  Bytes that
+ * follow a Number_of_Sequences of 0 inside its block are ignored.
+ * A plan / batch flag, accepted wherever plan flags are: zd_plan_create, _dict,
+ * _dicts, _device, zd_decompress*, every zd_batch_create*, the re-plans inside
+ * zd_plan_decompress and zd_batch_results (which keep it), and the sharded
+ * calls, which pass it to their plans; a seekable read takes it as the read
+ * option ZD_SEEK_RFC of zd_seekable_read_create_ex; zd_chunk_sizes_device has ZD_SIZES_RFC.  A dictionary's own tables
+ * (zd_dict_create takes no flags) are parsed by the reference's rule.
+ * zd_context / zd_block_decode / zd_execute_sequences take no flags and stay
+ * the reference's.  Without the flag nothing changes. */
+#define ZD_F_RFC 16384u
 
 /* zd_plan_info.executors: */
 #define ZD_EXEC_FUSED 1u   /* zd_k_fused: tables, FSE chains and execution per group of four
@@ -880,12 +916,16 @@ int  zd_batch_chain_info(const zd_batch* batch, uint32_t* levels, uint64_t* link
  * set (an empty Raw literals section is then accepted, as in a dictionary
  * plan; without it such a chunk is ZD_E_EMPTY_SLICE), a prefix batch included;
  * ZD_SIZES_LONG_WINDOW when they will be decoded with ZD_F_LONG_WINDOW (a
- * Window_Size up to 2 GiB is then no failure; the bit is that flag's own).
+ * Window_Size up to 2 GiB is then no failure; the bit is that flag's own);
+ * ZD_SIZES_RFC when they will be decoded with ZD_F_RFC (the walk then reads
+ * section headers as that flag does: the long-form Number_of_Sequences, an
+ * empty Raw literals section, an empty Huffman stream; the bit is that flag's own).
  * ZD_E_INVALID_ARG, before any HIP call: a NULL d_src_ptrs, d_src_bytes or
  * d_size with nchunks > 0, nchunks >= 2^31, unknown flag bits.  nchunks == 0 is
  * ZD_OK without a HIP call. */
 #define ZD_SIZES_DICT 1u
 #define ZD_SIZES_LONG_WINDOW 2048u   /* the chunks will be decoded with ZD_F_LONG_WINDOW (the same bit) */
+#define ZD_SIZES_RFC 16384u          /* the chunks will be decoded with ZD_F_RFC (the same bit) */
 int  zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
                            uint32_t flags, uint64_t* d_size, int32_t* d_status, uint8_t* d_exact, void* stream);
 /* zd_batch_create_device without destinations: a PACKED batch lays its outputs
@@ -1086,6 +1126,12 @@ int  zd_seekable_read_create(zd_seekable* z, const uint64_t* d_off, const uint64
  * the archive format's integrity mechanism -- of every needed entry, as zstd's
  * own seekable reader does on every read. */
 #define ZD_SEEK_VERIFY_TABLE 1u
+/* ZD_SEEK_RFC: the inner batch is created with ZD_F_RFC, so the archive's
+ * frames decode as RFC 8878 and libzstd have them.  A read option and not the
+ * plan flag: bit 16384 of `flags` has been ZD_E_INVALID_ARG in both calls since
+ * they exist, and stays so; the option's own bit is 4, bits 2 and 3 of
+ * read_flags being rejected likewise. */
+#define ZD_SEEK_RFC 4u
 /* zd_seekable_read_create with a read option word; read_flags 0 is that call.
  * Two more ZD_E_INVALID_ARG cases for the whole call, both before any HIP call
  * of this function: unknown read_flags bits; ZD_SEEK_VERIFY_TABLE on an

@@ -21,9 +21,14 @@ constexpr uint64_t MAX_WIN_SIZE = 8ull << 20;    // frame.rs:44
 constexpr uint64_t MAX_WIN_SIZE_LONG = 1ull << 31;   // with ZD_F_LONG_WINDOW (no executor depends on the window)
 // The walk's options (zd_walk.h index_frame / index_chunk): parse_compressed's
 // rfc_empty_lits (dictionary, set and prefix plans), ZD_F_LONG_WINDOW's limit
-constexpr uint32_t WALK_RFC_EMPTY_LITS = 1u, WALK_LONG_WINDOW = 2u;
-ZD_HD inline uint32_t walk_opts(bool rfc_empty_lits, bool long_window) {
-  return (rfc_empty_lits ? WALK_RFC_EMPTY_LITS : 0u) | (long_window ? WALK_LONG_WINDOW : 0u);
+// WALK_RFC (ZD_F_RFC): the section headers as RFC 8878 has them -- the long-form
+// Number_of_Sequences adds 0x7F00 (D1), Huffman stream sizes keep their bits
+// above 16 and an empty stream among a section's is ZD_E_CORRUPTED_STREAMS_SIZE
+// (D8); it comes with WALK_RFC_EMPTY_LITS
+constexpr uint32_t WALK_RFC_EMPTY_LITS = 1u, WALK_LONG_WINDOW = 2u, WALK_RFC = 4u;
+ZD_HD inline uint32_t walk_opts(bool rfc_empty_lits, bool long_window, bool rfc = false) {
+  return ((rfc_empty_lits || rfc) ? WALK_RFC_EMPTY_LITS : 0u) | (long_window ? WALK_LONG_WINDOW : 0u) |
+         (rfc ? WALK_RFC : 0u);
 }
 constexpr uint32_t MAX_BLOCK_OUT = 128u << 10;   // RFC Block_Maximum_Size (capacity bound only)
 
@@ -361,7 +366,7 @@ struct CompBlock {
   uint32_t huf_desc_size;  // bytes of the Huffman tree description (header byte included)
   uint32_t streams;        // rel: first Huffman stream (after the jump table)
   uint32_t stream_size[4]; // Huffman stream sizes after the reference's u16 truncation (literals.rs:115-122)
-  uint32_t nseq;           // Number_of_Sequences as the reference computes it (D1 kept)
+  uint32_t nseq;           // Number_of_Sequences as the reference computes it (D1 kept; RFC 8878's with WALK_RFC)
   uint32_t seq_tables;     // rel: first byte after nbSeq + mode byte
   uint32_t lut_slot;       // Huffman LUT slot this block builds (LIT_COMPRESSED)
   uint32_t fse_slot;       // FSE slot this block builds (nseq > 0)
@@ -376,7 +381,11 @@ struct CompBlock {
   uint8_t host_stage;      // GPU parse runs only parse stages < host_stage
   uint8_t prebuilt;        // 1: tables already present in the slots (context API); skip
   uint8_t seq_direct;      // 1: the sequence records are direct {ll, ml, offset_value} (zd_common.h)
+  uint8_t rfc;             // 1: a ZD_F_RFC plan's block (plan_frame writes it): K1 takes the Huffman weights by
+                           // RFC 8878 (huf_close), K2 enforces Regenerated_Size.  One of the struct's padding bytes
 };
+
+static_assert(sizeof(CompBlock) == 128, "CompBlock: 122 bytes and padding");
 
 // Results per compressed block (device).
 struct CompState {

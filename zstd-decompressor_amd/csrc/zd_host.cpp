@@ -178,8 +178,10 @@ struct zd_plan {
     return chain_on_j() ? jpend_chain_words((uint32_t)chain_count.size()) : JPEND_WORDS;
   }
   bool with_dict() const { return dict != nullptr || dset != nullptr || prefix; }
-  // the walk's options (zd_walk.h): parse_compressed's rfc_empty_lits, ZD_F_LONG_WINDOW
-  uint32_t walk_opts() const { return zd::walk_opts(with_dict(), (flags & ZD_F_LONG_WINDOW) != 0); }
+  // the walk's options (zd_walk.h): parse_compressed's rfc_empty_lits, ZD_F_LONG_WINDOW, ZD_F_RFC
+  uint32_t walk_opts() const {
+    return zd::walk_opts(with_dict(), (flags & ZD_F_LONG_WINDOW) != 0, (flags & ZD_F_RFC) != 0);
+  }
   std::vector<HostPart> parts;          // the host walk's frames, in input order
   std::vector<size_t> part_f0;          // plan frame index of each part's first frame
   size_t nframes = 0;
@@ -3149,11 +3151,12 @@ int zd_batch_bind_output(zd_batch* B, void* d_out, uint64_t cap) {
 
 int zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks, uint32_t flags,
                           uint64_t* d_size, int32_t* d_status, uint8_t* d_exact, void* stream) {
-  if ((flags & ~(ZD_SIZES_DICT | ZD_SIZES_LONG_WINDOW)) || nchunks >= (1ull << 31)) return ZD_E_INVALID_ARG;
+  if ((flags & ~(ZD_SIZES_DICT | ZD_SIZES_LONG_WINDOW | ZD_SIZES_RFC)) || nchunks >= (1ull << 31)) return ZD_E_INVALID_ARG;
   if (nchunks && (!d_src_ptrs || !d_src_bytes || !d_size)) return ZD_E_INVALID_ARG;
   if (!nchunks) return ZD_OK;
   HIPCHK(launch_chunk_sizes((const uint64_t*)d_src_ptrs, d_src_bytes, (uint32_t)nchunks,
-                            walk_opts((flags & ZD_SIZES_DICT) != 0, (flags & ZD_SIZES_LONG_WINDOW) != 0), d_size, d_status, d_exact, (hipStream_t)stream));
+                            walk_opts((flags & ZD_SIZES_DICT) != 0, (flags & ZD_SIZES_LONG_WINDOW) != 0,
+                                      (flags & ZD_SIZES_RFC) != 0), d_size, d_status, d_exact, (hipStream_t)stream));
   return ZD_OK;
 }
 
@@ -3510,8 +3513,9 @@ int zd_seekable_read_create_ex(zd_seekable* z, const uint64_t* d_off, const uint
                                zd_seek_read** out) {
   // ---- argument checks: no HIP call before they are done (z is looked at last) ----
   if (!out || (flags & ZD_F_SKIPPABLE) || (flags & ~(SEEK_READ_FLAGS | ZD_F_SKIPPABLE)) || nranges >= (1ull << 31) ||
-      (read_flags & ~ZD_SEEK_VERIFY_TABLE))
+      (read_flags & ~(ZD_SEEK_VERIFY_TABLE | ZD_SEEK_RFC)))
     return ZD_E_INVALID_ARG;
+  if (read_flags & ZD_SEEK_RFC) flags |= ZD_F_RFC;               // the inner batch's flag (zd.h: why a read option)
   if (nranges && (!d_off || !d_len || !d_dst)) return ZD_E_INVALID_ARG;
   if (!z || !z->p) return ZD_E_INVALID_ARG;
   const bool verify = (read_flags & ZD_SEEK_VERIFY_TABLE) != 0;

@@ -26,6 +26,7 @@
 #include "../../include/zd.h"
 #include "zd_chain.h"
 #include "zd_common.h"
+#include "zd_huf.h"
 #include "zd_launch.h"
 #include "zd_walk.h"
 
@@ -525,7 +526,7 @@ __device__ int k1_weight_stream(const uint8_t* desc, const uint8_t* src, const u
 // a tree of 256 symbols) returns K1_HUGE: the third pass takes the block.
 template <typename LN>
 __device__ int k1_huffman_lane(const uint8_t* desc, const uint8_t* src, const uint8_t* src_end, LN& L,
-                               uint16_t* __restrict__ lut, int* p_out) {
+                               uint16_t* __restrict__ lut, int* p_out, bool rfc) {
   int st = 0;
   uint32_t nw = 0;
   const uint8_t h = desc[0];
@@ -548,7 +549,7 @@ __device__ int k1_huffman_lane(const uint8_t* desc, const uint8_t* src, const ui
   K1T(h1);
   K1ADD(3, h0, h1);
   // from_weights (huffman.rs:177-203)
-  uint32_t sum = 0;
+  uint32_t sum = 0, maxw = 0;
   for (uint32_t i = 0; i < nw; i++) {
     const uint32_t w = L.weights[i];
     if (!w) continue;
@@ -556,17 +557,11 @@ __device__ int k1_huffman_lane(const uint8_t* desc, const uint8_t* src, const ui
     const uint32_t add = 1u << (w - 1);
     if (sum > 0xFFFFFFFFu - add) return ZD_E_REF_PANIC;
     sum += add;
+    maxw = w > maxw ? w : maxw;
   }
-  if (sum == 0) return ZD_E_REF_PANIC;
-  int p = highbit32(sum);
-  if ((1ull << p) < sum) p++;
-  if (p >= 32) return ZD_E_REF_PANIC;
-  const uint8_t rest = (uint8_t)((1u << p) - sum);
-  if (rest == 0) return ZD_E_REF_PANIC;           // D3
-  const uint32_t manquant = (uint32_t)highbit32(rest) + 1;
-  for (uint32_t i = 0; i < nw; i++)
-    if (L.weights[i] > (uint32_t)p + 1) return ZD_E_REF_PANIC;
-  if (manquant > (uint32_t)p + 1) return ZD_E_REF_PANIC;
+  int p;
+  uint32_t manquant;
+  if (int r = huf_close(sum, maxw, rfc, &p, &manquant)) return r;   // (zd_huf.h: D3, or RFC 8878's rule)
   L.weights[nw] = (uint8_t)manquant;          // the implied last symbol: width p + 1 - manquant
   const uint32_t n = nw + 1;
   if (p > LUT_MAX_BITS) {
@@ -705,7 +700,8 @@ __global__ __launch_bounds__(K1_LANES) void zd_k_tables(const uint8_t* __restric
   const uint8_t* blk = src + C.src;
   if ((PART & 1) && C.lit_type == LIT_COMPRESSED && C.host_stage > PS_HUF_DESC) {
     int p = 0;
-    const int st = k1_huffman_lane(blk + C.lit_data, src, src + src_size, L, luts + (uint64_t)C.lut_slot * LUT_ENTRIES, &p);
+    const int st = k1_huffman_lane(blk + C.lit_data, src, src + src_size, L, luts + (uint64_t)C.lut_slot * LUT_ENTRIES, &p,
+                                   C.rfc != 0);
     if (!BIG && st == K1_BIG) {
       cstate[ci].k1_bigh = 1;
       return;
@@ -765,7 +761,7 @@ struct K1LaneH {
 };
 
 __device__ int k1_huffman_huge(const uint8_t* desc, const uint8_t* src, const uint8_t* src_end, K1LaneH& L,
-                               uint16_t* lut, int* p_out, uint32_t* deep) {
+                               uint16_t* lut, int* p_out, uint32_t* deep, bool rfc) {
   uint32_t sum = 0, maxw = 0, nw = 0;
   bool panic = false;
   int st = k1_weight_stream(desc, src, src_end, L, [&](uint32_t, uint32_t w) {
@@ -777,14 +773,10 @@ __device__ int k1_huffman_huge(const uint8_t* desc, const uint8_t* src, const ui
     return true;
   }, &nw);
   if (st) return st;
-  if (panic || sum == 0) return ZD_E_REF_PANIC;
-  int p = highbit32(sum);
-  if ((1ull << p) < sum) p++;
-  if (p >= 32) return ZD_E_REF_PANIC;
-  const uint8_t rest = (uint8_t)((1u << p) - sum);
-  if (rest == 0) return ZD_E_REF_PANIC;           // D3
-  const uint32_t manquant = (uint32_t)highbit32(rest) + 1;
-  if (maxw > (uint32_t)p + 1 || manquant > (uint32_t)p + 1) return ZD_E_REF_PANIC;
+  if (panic) return ZD_E_REF_PANIC;
+  int p;
+  uint32_t manquant;
+  if (int r = huf_close(sum, maxw, rfc, &p, &manquant)) return r;   // (zd_huf.h: D3, or RFC 8878's rule)
   for (int w = 0; w <= p; w++)
     for (int b = 0; b < 256; b++) L.cnt[w][b] = 0;
   uint32_t nw2 = 0;
@@ -852,7 +844,7 @@ __global__ __launch_bounds__(K1H_LANES) void zd_k_tables_huge(const uint8_t* __r
     const CompBlock C = comp[ci];
     int p = 0;
     const int st = k1_huffman_huge(src + C.src + C.lit_data, src, src + src_size, L,
-                                   luts + (uint64_t)C.lut_slot * LUT_ENTRIES, &p, deep);
+                                   luts + (uint64_t)C.lut_slot * LUT_ENTRIES, &p, deep, C.rfc != 0);
     if (st == ZD_E_OUT_OF_DOMAIN)
       key_min(fstate, C.frame, make_key(PH_DECODE, C.block_in_frame, DS_LITERALS, 0, ZD_E_OUT_OF_DOMAIN));
     else if (st)
@@ -1164,7 +1156,7 @@ __global__ __launch_bounds__(64) void zd_k_dict_tables(const uint8_t* __restrict
       if (pos + sz > n) {
         st = ZD_E_DICT_CORRUPTED;
       } else {
-        st = k1_huffman_lane(d + 8, d, d + n, L, lut, &p);
+        st = k1_huffman_lane(d + 8, d, d + n, L, lut, &p, false);   // zd_dict_create takes no flags
         if (st > 0 || (!st && p > K2_LUT_BITS)) st = ZD_E_OUT_OF_DOMAIN;   // (K1_HUGE: more than 255 weights)
         pos += sz;
       }
@@ -1531,12 +1523,17 @@ __global__ __launch_bounds__(K2_LANES) void zd_k_huffman(const uint8_t* __restri
       total += counts[b][j];
     }
     const bool fits = total <= R + 16 + C.lit_extra;   // the block's literal slot
-    if (!rfc && !err && !fits)
+    // a ZD_F_RFC plan's block (D8): streams that do not hold exactly their
+    // shares of Regenerated_Size fail the frame; nothing is laid out again
+    const bool bad = C.rfc && !err && (!rfc || total != R);
+    if (bad)
+      key_min(fstate, C.frame, make_key(PH_DECODE, C.block_in_frame, DS_LITERALS, 0, ZD_E_CORRUPTED_STREAMS_SIZE));
+    else if (!rfc && !err && !fits)
       key_min(fstate, C.frame,
               make_key(PH_DECODE, C.block_in_frame, DS_LITERALS, DS_LIT_OVERFLOW_SUB, ZD_E_OUT_OF_DOMAIN));
-    redo[b] = !rfc && !err && fits;
+    redo[b] = !rfc && !err && fits && !bad;
     cstate[ci].lit_count = total;
-    if (err || (!rfc && !fits)) cstate[ci].stop = 1;
+    if (err || bad || (!rfc && !fits)) cstate[ci].stop = 1;
   }
   __syncthreads();
   if (act && k < m && redo[b]) {
@@ -4037,7 +4034,7 @@ static_assert(sizeof(K1LaneP) == 260, "K1LaneP: 65 dwords");
 // weights: k1_huffman_lane's statuses, K1_BIG for what the build pass does
 // not take.
 __device__ int k1_huffman_parse(const uint8_t* desc, const uint8_t* src, const uint8_t* src_end, K1LaneP& L,
-                                uint32_t* rec, int* p_out) {
+                                uint32_t* rec, int* p_out, bool rfc) {
   int st = 0;
   uint32_t nw = 0, sum = 0, maxw = 0, acc = 0;
   bool panic = false;
@@ -4065,14 +4062,10 @@ __device__ int k1_huffman_parse(const uint8_t* desc, const uint8_t* src, const u
   }
   if (st > 0) return K1_BIG;
   if (st) return st;
-  if (panic || sum == 0) return ZD_E_REF_PANIC;
-  int p = highbit32(sum);
-  if ((1ull << p) < sum) p++;
-  if (p >= 32) return ZD_E_REF_PANIC;
-  const uint8_t rest = (uint8_t)((1u << p) - sum);
-  if (rest == 0) return ZD_E_REF_PANIC;           // D3
-  const uint32_t manquant = (uint32_t)highbit32(rest) + 1;
-  if (maxw > (uint32_t)p + 1 || manquant > (uint32_t)p + 1) return ZD_E_REF_PANIC;
+  if (panic) return ZD_E_REF_PANIC;
+  int p;
+  uint32_t manquant;
+  if (int r = huf_close(sum, maxw, rfc, &p, &manquant)) return r;   // (zd_huf.h: D3, or RFC 8878's rule)
   // a complete tree (the codes fill the 2^p prefixes: no hole, every code
   // placed) of at most K2's LUT bits
   if (p > K2_LUT_BITS || (uint64_t)sum + (1u << (manquant - 1)) != (1ull << p)) return K1_BIG;
@@ -4143,7 +4136,7 @@ __global__ __launch_bounds__(K1P_LANES) void zd_k_tables_parse(const uint8_t* __
   if ((PART & 1) && C.lit_type == LIT_COMPRESSED && C.host_stage > PS_HUF_DESC) {
     int p = 0;
     const int st = k1_huffman_parse(blk + C.lit_data, src, src + src_size, lanes[(PART & 1) ? threadIdx.x : 0],
-                                    (uint32_t*)(luts + (uint64_t)C.lut_slot * LUT_ENTRIES), &p);
+                                    (uint32_t*)(luts + (uint64_t)C.lut_slot * LUT_ENTRIES), &p, C.rfc != 0);
     if (st == K1_BIG) {
       cstate[ci].k1_bigh = 1;                     // zd_k_tables<true> builds this tree
     } else if (st) {
@@ -4746,7 +4739,10 @@ __global__ __launch_bounds__(K4F_T) void zd_k_execute_lds(const uint8_t* __restr
         st3[0] = rc_apply(ex[0], in); st3[1] = rc_apply(ex[1], in); st3[2] = rc_apply(ex[2], in);
       }
 #pragma unroll
-      for (int k = 0; k < K4F_KC; k++) oc[k] = rep_step(st3, oc[k], ll[k]);   // offset codes, concrete
+      // offset codes, concrete.  The padding past the chunk's last sequence gives its offset (1) and leaves
+      // the state alone: the thread that holds the last sequence hands st3 on as the state after the
+      // chunk, and a later block of the frame reads its repeat offsets from it
+      for (int k = 0; k < K4F_KC; k++) oc[k] = b0 + k < cn ? rep_step(st3, oc[k], ll[k]) : 1u;
       const uint32_t pbase = pos + L.wsum[wv][0] + (it - stot);      // frame position of the first literal
       const uint32_t lbase = lit_cursor + L.wsum[wv][1] + (il - slit);
       const uint32_t ctot = L.tot[0], clit = L.tot[1];

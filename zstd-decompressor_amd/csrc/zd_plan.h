@@ -291,6 +291,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   }
   fd.out_len0 = out_len0;
   const bool frame_failed_host = fs.key != KEY_NONE;
+  const bool rfc = (X.flags & ZD_F_RFC) != 0;
   // bytes of the frame's region before its first own byte (the context API's existing output)
   const uint64_t own0 = X.dict ? 0 : out_len0;
   uint64_t jseg = 0;
@@ -306,6 +307,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
       cb.frame = fi;
       cb.block_in_frame = bi;
       cb.prebuilt = 0;
+      cb.rfc = rfc ? 1 : 0;
       cb.huf_src = -1;
       cb.tab_src[0] = cb.tab_src[1] = cb.tab_src[2] = -1;
       const uint32_t ci = (uint32_t)c.comps;
@@ -320,7 +322,11 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
       if (cb.lit_type == LIT_COMPRESSED && cb.host_stage > PS_HUF_DESC) cb.lut_slot = (uint32_t)c.luts++;
       // sequences: Repeat resolution (sequences.rs:147-187, 232-234)
       if (!failing) {
-        if (cb.nseq == 0) {
+        if (cb.nseq == 0 && rfc) {
+          // RFC 8878 (D2): the block's literals are its output; it builds no
+          // table and leaves tab_prev, so a later Repeat_Mode reaches across it
+          // (huf_prev above moves only with a tree of the block's own)
+        } else if (cb.nseq == 0) {
           int code = ZD_E_EMPTY_INPUT_DATA;
           for (int k = 0; k < 3; k++) if (tab_prev[k] < 0) { code = ZD_E_NO_PREVIOUS_DECODER; break; }
           fs.key = plan_min(fs.key, make_key(PH_DECODE, bi, DS_SEQUENCES, 0, code));

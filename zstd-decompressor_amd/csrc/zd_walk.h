@@ -72,8 +72,16 @@ ZD_HD inline void zero_bytes(void* p, size_t n) {
 // section of 0 bytes is accepted as RFC 8878 has it -- a record found wholly in
 // the dictionary has no literals -- where the reference's zero-length slice is
 // an EmptySliceError (parsing.rs, kept everywhere else).
+// wopt: the walk's options (zd_common.h walk_opts; WALK_LONG_WINDOW is not read
+// here).  WALK_RFC_EMPTY_LITS is the above.  WALK_RFC (ZD_F_RFC) reads the
+// headers as RFC 8878 has them: the three-byte Number_of_Sequences adds 0x7F00
+// where the reference adds 0x7F (D1); the sizes of Huffman streams are not
+// truncated to 16 bits, and a section one of whose streams is empty is
+// ZD_E_CORRUPTED_STREAMS_SIZE where the reference decodes the streams before it
+// (D8: such a section cannot hold its Regenerated_Size).
 ZD_HD inline int parse_compressed(const uint8_t* base, uint64_t off, uint32_t size, CompBlock* cb, WalkErr* e,
-                                  bool rfc_empty_lits = false) {
+                                  uint32_t wopt = 0) {
+  const bool rfc_empty_lits = (wopt & WALK_RFC_EMPTY_LITS) != 0, rfc = (wopt & WALK_RFC) != 0;
   Bytes np{base + off, size};
   const uint8_t* start = np.p;
   auto rel = [&]() { return (uint32_t)(np.p - start); };
@@ -136,9 +144,9 @@ ZD_HD inline int parse_compressed(const uint8_t* base, uint64_t off, uint32_t si
       if (int r = ni.le(2, &s3)) return e->code = r;
       if (s1 + s2 + s3 > total - 6) return e->code = ZD_E_CORRUPTED_STREAMS_SIZE;
       size_t s4 = total - 6 - s1 - s2 - s3;
-      ss[0] = (uint32_t)s1; ss[1] = (uint32_t)s2; ss[2] = (uint32_t)s3; ss[3] = (uint16_t)s4;
+      ss[0] = (uint32_t)s1; ss[1] = (uint32_t)s2; ss[2] = (uint32_t)s3; ss[3] = rfc ? (uint32_t)s4 : (uint16_t)s4;
     } else {
-      ss[0] = (uint16_t)ni.n;
+      ss[0] = rfc ? (uint32_t)ni.n : (uint16_t)ni.n;
     }
     cb->streams = (uint32_t)(ni.p - start);
     const uint8_t* d;
@@ -149,6 +157,7 @@ ZD_HD inline int parse_compressed(const uint8_t* base, uint64_t off, uint32_t si
       cb->stream_size[k] = ss[k];
       cb->nstreams = (uint8_t)(k + 1);
     }
+    if (rfc && cb->nstreams != nstreams) return e->code = ZD_E_CORRUPTED_STREAMS_SIZE;
   }
   // Sequences::parse (sequences.rs:52-75)
   e->stage = PS_SEQ_HDR;
@@ -162,7 +171,7 @@ ZD_HD inline int parse_compressed(const uint8_t* base, uint64_t off, uint32_t si
     uint8_t b1, b2;
     if (int r = np.u8(&b1)) return e->code = r;
     if (int r = np.u8(&b2)) return e->code = r;
-    nseq = (uint32_t)b1 + ((uint32_t)b2 << 8) + 0x7F;     // D1 (sequences.rs:84)
+    nseq = (uint32_t)b1 + ((uint32_t)b2 << 8) + (rfc ? 0x7F00u : 0x7Fu);     // D1 (sequences.rs:84)
   }
   cb->nseq = nseq;
   cb->modes[0] = cb->modes[1] = cb->modes[2] = M_REPEAT;
@@ -220,7 +229,7 @@ ZD_HD inline int parse_header(Bytes& in, zd_frame_desc* f) {
 // Walks one frame at in, handing its blocks to the sink (S.size(): blocks
 // so far; S.push(block)).  On error, hf->key/status hold the failure; the
 // blocks parsed before (and the failing one, with its host_stage) are kept.
-// wopt: WALK_RFC_EMPTY_LITS (parse_compressed's rfc_empty_lits) and
+// wopt: WALK_RFC_EMPTY_LITS and WALK_RFC (parse_compressed's) and
 // WALK_LONG_WINDOW (ZD_F_LONG_WINDOW: a Window_Size up to MAX_WIN_SIZE_LONG,
 // 2 GiB, where the reference's MAX_WIN_SIZE stands otherwise).
 template <typename SINK>
@@ -283,7 +292,7 @@ ZD_HD inline int index_frame(const uint8_t* base, Bytes& in, HostFrame* hf, SINK
         cb.block_in_frame = bi;
         cb.host_stage = PS_ALL;
         WalkErr e;
-        int r = parse_compressed(base, hb.src, hb.size, &cb, &e, (wopt & WALK_RFC_EMPTY_LITS) != 0);
+        int r = parse_compressed(base, hb.src, hb.size, &cb, &e, wopt);
         if (r) {
           cb.host_stage = (uint8_t)e.stage;
           push(hb);

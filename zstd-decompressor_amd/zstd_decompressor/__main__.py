@@ -46,6 +46,9 @@ meaning: the frames' own Content_Checksums.
 --long accepts frames whose Window_Size is up to 2 GiB (F_LONG_WINDOW; the
 default is the reference's 8 MiB limit): what `zstd --long` and `zstd
 --patch-from` write for inputs past 8 MiB.
+--rfc decodes frames as RFC 8878 and libzstd have them (F_RFC; the default is
+the reference's decoder, which fails on a compressed block without sequences
+and on some Huffman weight totals, and miscounts more than 32,511 sequences).
 """
 from __future__ import annotations
 
@@ -58,6 +61,12 @@ from .batch import Dictionary, DictionarySet, Plan, chunk_sizes, decode_tensors,
 # --patch-from: a frame of at least this Frame_Content_Size goes to the block-parallel executor (K4J_MIN_BLOCKS
 # blocks of 128 KiB, zd_plan.h: the plain plans' own threshold in bytes the command line can see)
 PATCH_BLOCK_PARALLEL_BYTES = 16 * (128 << 10)
+
+
+def _plan_flags(a) -> int:
+    """--verify, --long and --rfc as plan flags"""
+    return ((_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0) |
+            (_lib.F_RFC if a.rfc else 0))
 
 
 def _info(data: bytes) -> int:
@@ -101,6 +110,9 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--long", dest="long_window", action="store_true",
                     help="accept frames whose Window_Size is up to 2 GiB (default: 8 MiB, the reference's limit), "
                          "as written by zstd --long and by --patch-from on large files (not in the reference)")
+    ap.add_argument("--rfc", action="store_true",
+                    help="decode frames as RFC 8878 and libzstd have them, where the default keeps the reference's "
+                         "departures from the format (not in the reference)")
     ap.add_argument("--range", dest="byte_range", metavar="OFF:LEN",
                     help="read LEN content bytes from offset OFF of a zstd seekable archive, decoding only the "
                          "entries they lie in (not in the reference; not together with -D or --patch-from)")
@@ -126,7 +138,7 @@ def _range(a, data: bytes) -> int:
     except _lib.ZdError as e:
         print(f"Error: not a seekable archive: {e.name}", file=sys.stderr)
         return 1
-    flags = (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0)
+    flags = _plan_flags(a)
     try:
         out = bytes(arc.read(off, length, flags=flags, verify_table=a.verify_table).cpu().numpy().tobytes())
     except _lib.ZdError as e:
@@ -158,7 +170,7 @@ def _verify_table(a, data: bytes) -> int:
         print(f"Error: not a seekable archive: {e.name}", file=sys.stderr)
         return 1
     try:
-        flags = (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0)
+        flags = _plan_flags(a)
         entries, statuses = arc.verify_all(flags=flags)
     except ValueError as e:
         print(f"Error: --verify-table: {e}", file=sys.stderr)
@@ -182,7 +194,7 @@ def _patch(a, data: bytes) -> int:
     if a.long_window:
         # (the host index takes no flags: the device's size query walks the chunk under the long limit, and as a
         # prefix batch walks it: an empty Raw literals section is accepted)
-        sizes, _, exact = chunk_sizes([d_src.data_ptr()], [len(data)], dictionary=True, long_window=True)
+        sizes, _, exact = chunk_sizes([d_src.data_ptr()], [len(data)], dictionary=True, long_window=True, rfc=a.rfc)
         cap = int(sizes.cpu()[0])
         fcs = cap if int(exact.cpu()[0]) else None
     else:
@@ -194,7 +206,7 @@ def _patch(a, data: bytes) -> int:
             fcs = cs if cs != (1 << 64) - 1 else None
             cap = max(cap, cs if fcs is not None else (128 << 10) * max(f["num_blocks"], 1))
     d_dst = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-    flags = (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0)
+    flags = _plan_flags(a)
     if fcs is not None and fcs >= PATCH_BLOCK_PARALLEL_BYTES:
         flags |= _lib.F_BLOCK_PARALLEL
     status, length = decode_tensors([d_src], [d_dst], flags=flags, prefixes=[up(old)])
@@ -249,7 +261,7 @@ def main(argv=None) -> int:
         print(f"Error: dictionary: {e.name}", file=sys.stderr)
         return 1
     plan = Plan(data, a.print_skippable,
-                (_lib.F_VERIFY_CHECKSUM if a.verify else 0) | (_lib.F_LONG_WINDOW if a.long_window else 0),
+                _plan_flags(a),
                 dictionary=dictionary)
     dev = torch.device("cuda", torch.cuda.current_device())
     d_src = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)

@@ -315,7 +315,10 @@ F_VERIFY_CHECKSUM = 1024  # Content_Checksums verified inside the decode launch 
 F_LONG_WINDOW = 2048   # accept a Window_Size up to 2 GiB (default: the reference's 8 MiB limit)
 F_CHAIN_BLOCK_PARALLEL = 4096  # a chain batch (parents=): frames with a compressed block -> K4J, level by level
 F_AUTO_EXECUTOR = 8192  # a prefix or chain batch: each chunk's executor by rule (include/zd.h ZD_AUTO_*)
+SEEK_RFC = 4           # zd_seekable_read_create_ex read_flags: the inner batch decodes with F_RFC
 SEEK_VERIFY_TABLE = 1  # zd_seekable_read_create_ex read_flags: the seek table's Checksums verified inside the launch
 SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
+F_RFC = 16384           # frames decode as RFC 8878 / libzstd have them (default: the reference's decoder, D1-D3, D8)
+SIZES_RFC = 16384        # zd_chunk_sizes_device: the chunks will be decoded with F_RFC (the same bit)
 SIZES_LONG_WINDOW = 2048  # zd_chunk_sizes_device: the chunks will be decoded with F_LONG_WINDOW (the same bit)
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)

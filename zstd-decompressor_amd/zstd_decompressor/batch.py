@@ -125,12 +125,16 @@ def _decompress(data: bytes, flags: int, dictionary=None):
         plan.close()
 
 
-def decompress(data: bytes, print_skippable: bool = False, dictionary=None, verify: bool = False) -> bytes:
+def decompress(data: bytes, print_skippable: bool = False, dictionary=None, verify: bool = False,
+               rfc: bool = False) -> bytes:
     """Decode every frame of `data` on the GPU (host in, host out);
     dictionary: a Dictionary every frame decodes with, or a DictionarySet;
     verify: a frame whose bytes do not hash to its Content_Checksum raises
-    ZdError(CHECKSUM_WRONG), as libzstd fails such a frame."""
-    flags = (_lib.F_SKIPPABLE if print_skippable else 0) | (_lib.F_VERIFY_CHECKSUM if verify else 0)
+    ZdError(CHECKSUM_WRONG), as libzstd fails such a frame; rfc: frames decode
+    as RFC 8878 and libzstd have them (F_RFC), where the default is the
+    reference's decoder, which fails or corrupts some frames libzstd writes."""
+    flags = ((_lib.F_SKIPPABLE if print_skippable else 0) | (_lib.F_VERIFY_CHECKSUM if verify else 0) |
+             (_lib.F_RFC if rfc else 0))
     st, out = _decompress(data, flags, dictionary)
     _lib.check(st, "zd_decompress")
     return out
@@ -299,7 +303,8 @@ def _device_arrays(arrs, nchunks, lists=True):
     return n, addr, keep
 
 
-def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, stream=None, long_window: bool = False):
+def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, stream=None, long_window: bool = False,
+                rfc: bool = False):
     """zd_chunk_sizes_device: what each chunk needs of its destination, asked
     on the device.  src_ptrs / src_sizes as in Batch.from_device (device
     tensors, or addresses with `nchunks`).  Returns three device tensors
@@ -308,7 +313,8 @@ def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, str
     and RLE blocks, exact 0; 0 for a failing or empty chunk) and the status of
     its header walk.  dictionary=True when the chunks will be decoded with a
     Dictionary or DictionarySet, long_window=True when with F_LONG_WINDOW (a
-    Window_Size up to 2 GiB is then no failure).  The kernel is queued on
+    Window_Size up to 2 GiB is then no failure), rfc=True when with F_RFC (the
+    walk reads section headers as that flag does).  The kernel is queued on
     `stream` (torch's current stream by default) and nothing is synchronised."""
     import torch
     if stream is None:
@@ -321,7 +327,8 @@ def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, str
     ptr = lambda t: C.c_void_p(t.data_ptr() if n else 0)
     _lib.check(_lib.lib().zd_chunk_sizes_device(C.c_void_p(addr[0]), C.c_void_p(addr[1]), n,
                                                 (_lib.SIZES_DICT if dictionary else 0) |
-                                                (_lib.SIZES_LONG_WINDOW if long_window else 0), ptr(sizes), ptr(statuses),
+                                                (_lib.SIZES_LONG_WINDOW if long_window else 0) |
+                                                (_lib.SIZES_RFC if rfc else 0), ptr(sizes), ptr(statuses),
                                                 ptr(exact), C.c_void_p(stream)), "zd_chunk_sizes_device")
     return sizes, statuses, exact
 

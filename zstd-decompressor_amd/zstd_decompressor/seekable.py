@@ -101,7 +101,8 @@ class SeekableArchive:
         or a device tensor of addresses; range i is written at dsts[i].
         verify_table: every launch compares the table's Checksum of every
         needed entry (ZD_SEEK_VERIFY_TABLE); ZdError INVALID_ARG on an archive
-        without checksums."""
+        without checksums.  _lib.F_RFC in flags reaches the inner batch as the
+        read option ZD_SEEK_RFC (the C call rejects the plan flag's bit)."""
         import torch
         from .batch import _device_arrays
         self._open()
@@ -121,8 +122,9 @@ class SeekableArchive:
         s = _stream(stream)
         h = C.c_void_p()
         _lib.check(_lib.lib().zd_seekable_read_create_ex(self._h, C.c_void_p(addr[0]), C.c_void_p(addr[1]),
-                                                         C.c_void_p(addr[2]), n, flags,
-                                                         _lib.SEEK_VERIFY_TABLE if verify_table else 0,
+                                                         C.c_void_p(addr[2]), n, flags & ~_lib.F_RFC,
+                                                         (_lib.SEEK_VERIFY_TABLE if verify_table else 0) |
+                                                         (_lib.SEEK_RFC if flags & _lib.F_RFC else 0),
                                                          C.c_void_p(s), C.byref(h)),
                    "zd_seekable_read_create_ex")
         return SeekReader(h, n, outputs, keep_dst, self)
