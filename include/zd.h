@@ -926,6 +926,16 @@ int  zd_batch_chain_info(const zd_batch* batch, uint32_t* levels, uint64_t* link
 #define ZD_SIZES_DICT 1u
 #define ZD_SIZES_LONG_WINDOW 2048u   /* the chunks will be decoded with ZD_F_LONG_WINDOW (the same bit) */
 #define ZD_SIZES_RFC 16384u          /* the chunks will be decoded with ZD_F_RFC (the same bit) */
+/* ZD_SIZES_MULTI_FRAME: the chunks will be decoded by a multi-frame batch
+ * (zd_multi_create_device), so a chunk may hold any number of concatenated zstd
+ * frames.  It is cut into sub-chunks as that call cuts it; d_size[i] is the sum
+ * of the sub-chunks' reserves (a destination of that many bytes never makes the
+ * chunk ZD_E_DST_TOO_SMALL), d_exact[i] is 1 when every sub-chunk's reserve is
+ * its frame's Frame_Content_Size (0 for a chunk that ends in skippable frames,
+ * or of no bytes), d_status[i] the walk status of the first sub-chunk that
+ * fails: a second zstd frame is no failure here.  Without the flag every output
+ * is as it always was.  (Bits 2 and 4 of the word stay ZD_E_INVALID_ARG.) */
+#define ZD_SIZES_MULTI_FRAME 8u
 int  zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks,
                            uint32_t flags, uint64_t* d_size, int32_t* d_status, uint8_t* d_exact, void* stream);
 /* zd_batch_create_device without destinations: a PACKED batch lays its outputs
@@ -1213,6 +1223,109 @@ typedef struct zd_seek_read_info2 {
  * fewer than sizeof(zd_seek_read_info) is ZD_E_INVALID_ARG. */
 int  zd_seek_read_info_get_sized(const zd_seek_read* r, zd_seek_read_info* info, size_t bytes);
 void zd_seek_read_destroy(zd_seek_read* r);
+
+/* ------------------------------------------------------------------ */
+/* Multi-frame batches: a batch whose chunks hold any number of         */
+/* concatenated zstd frames (RFC 8878: a zstd payload), as a streaming  */
+/* compressor that closes a frame at every flush, `cat a.zst b.zst`,    */
+/* pzstd or a log appended to frame by frame write them.  zd_batch_*    */
+/* keeps ZD_E_OUT_OF_DOMAIN for a second frame in a chunk; this object  */
+/* is an ordinary device-built batch over the chunks' SUB-CHUNKS, made  */
+/* on the GPU, plus two passes behind its decode.                       */
+/* ------------------------------------------------------------------ */
+typedef struct zd_multi zd_multi;
+
+/* zd_batch_create_device's four DEVICE arrays (readable on `stream`, released
+ * when the call returns if the caller likes; the sources too: the inner batch
+ * gathers them), its flags, and at most one of dict / set.
+ * SUB-CHUNKS.  A chunk is walked from its first byte with the walk the inner
+ * batch uses.  Each zstd frame that walks to its end closes a sub-chunk: the
+ * bytes from the end of the previous zstd frame (or the chunk's start) to the
+ * end of this frame, so skippable frames travel with the frame behind them.
+ * Whatever remains -- skippable frames only, bytes that are no frame, a frame
+ * whose walk fails with everything behind it -- is one last sub-chunk when it
+ * is not empty; a chunk in which no zstd frame walks to its end is one
+ * sub-chunk, the whole chunk.  A sub-chunk's status is what
+ * zd_batch_create_device gives that byte range.
+ * PLACEMENT.  A sub-chunk's reserve and exactness are zd_chunk_sizes_device's.
+ * Sub-chunk k of chunk i is IN PLACE when every sub-chunk before it in the
+ * chunk is exact: it decodes at d_dst_ptrs[i] + the sum of their
+ * Frame_Content_Sizes, with capacity min(reserve, dst_cap_i - offset) when it
+ * is exact itself and dst_cap_i - offset when not (0 when the offset is past
+ * dst_cap_i: the inner batch's capacity pass then reports ZD_E_DST_TOO_SMALL).
+ * Every sub-chunk behind the first inexact one is STAGED: it decodes into a
+ * staging buffer the object owns (its reserve as its capacity, offsets rounded
+ * up to 16, from the workspace cache) and is copied behind the chunk's earlier
+ * bytes by every launch.  Frames that all carry a Frame_Content_Size stage
+ * nothing.
+ * RESULTS.  A chunk's status is that of its lowest-numbered sub-chunk that did
+ * not end ZD_OK; else ZD_E_DST_TOO_SMALL when the decoded lengths, summed in
+ * order, pass dst_cap_i at a staged sub-chunk; else ZD_OK with the summed
+ * length.  (A frame that ends ZD_OK with a length other than its
+ * Frame_Content_Size, with a frame in place behind it: ZD_E_OUT_OF_DOMAIN.)
+ * A failed chunk's length is 0 and its destination bytes are unspecified;
+ * nothing outside [dst_i, dst_i + dst_cap_i) is ever written and a failing
+ * chunk touches no other.  An entry zd_batch_create_device would refuse (a
+ * NULL address with a non-zero count, a range that wraps: ZD_E_INVALID_ARG; a
+ * chunk of 2^32 bytes or more: ZD_E_OUT_OF_DOMAIN) fails its chunk alone, and
+ * none of it is read or written.  Overlapping destinations are the caller's
+ * duty.
+ * Built on the GPU: zd_k_multi_count (one lane a chunk walks the headers where
+ * the chunk lies, at any alignment, no byte outside it), the scans,
+ * zd_k_multi_fill, then zd_batch_create_device (or its dictionary forms) with
+ * the caller's flags.  Host waits: one of its own (the sub-chunks, the staging
+ * bytes, the 32 KiB copy pieces come back) and the inner creation's.
+ * ZD_E_INVALID_ARG for the whole call, before any HIP call: out NULL, a NULL
+ * array with nchunks > 0, nchunks >= 2^31, both dict and set, ZD_F_SKIPPABLE,
+ * unknown flag bits.  ZD_E_OUT_OF_DOMAIN for the whole call: 2^31 sub-chunks
+ * or copy pieces, or more.
+ * Limits: no prefix, chain or packed multi-frame batches; device arrays only;
+ * the destinations are fixed at creation; one lane walks a chunk's headers, so
+ * one huge multi-frame file belongs in zd_plan_create_device. */
+int  zd_multi_create_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes,
+                            void* const* d_dst_ptrs, const uint64_t* d_dst_cap, size_t nchunks,
+                            uint32_t flags, const zd_dict* dict, const zd_dict_set* set,
+                            void* stream, zd_multi** out);
+/* Queues, in this order: the inner batch's decode; zd_k_multi_join, one lane a
+ * chunk over its sub-chunks' results (the chunk's status and length, each
+ * staged sub-chunk's final address, "not delivered" from the first failure or
+ * overflow on); zd_k_multi_copy over the 32 KiB pieces of the staged reserves
+ * (not queued by a batch that stages nothing), which loads only a sub-chunk's
+ * own decoded bytes in the staging buffer and stores only inside the chunk's
+ * destination.  The device result arrays are final behind these.  No
+ * allocation, no host synchronisation: capturable, and may be called again. */
+int  zd_multi_decode_async(zd_multi* m, void* stream);
+/* The join and copy passes alone, behind whatever `stream` holds (as
+ * zd_seek_read_finish_async).  ZD_E_INVALID_ARG before the first
+ * zd_multi_decode_async. */
+int  zd_multi_finish_async(zd_multi* m, void* stream);
+/* The per-chunk device arrays (nchunks entries each), owned by the object. */
+int  zd_multi_device_results(const zd_multi* m, const int32_t** d_status, const uint64_t** d_len);
+/* Waits and returns the same on the host (arrays of cap >= nchunks entries,
+ * either may be NULL) and the number of chunks that are not ZD_OK.  Runs the
+ * inner zd_batch_results -- a K4J frame that did not converge is decoded again
+ * there -- and then the join and copy passes once more. */
+int  zd_multi_results(zd_multi* m, void* stream, int32_t* status, uint64_t* len, size_t cap,
+                      uint64_t* nfailed);
+/* The sub-chunks: d_first has nchunks + 1 entries, chunk i's sub-chunks are
+ * d_first[i] .. d_first[i + 1) of the inner batch's result arrays
+ * d_frame_status / d_frame_len (NULL for a batch of no chunks).  Device arrays
+ * the object owns; any pointer may be NULL. */
+int  zd_multi_device_frames(const zd_multi* m, const uint64_t** d_first,
+                            const int32_t** d_frame_status, const uint64_t** d_frame_len);
+typedef struct zd_multi_info {
+  uint64_t nchunks;
+  uint64_t frames;             /* F: the sub-chunks, the inner batch's chunks */
+  uint64_t frames_in_place;    /*   of them, decoded in their chunk's destination */
+  uint64_t staged_frames;      /*   and decoded into the staging buffer */
+  uint64_t staged_bytes;       /* the staging buffer (every staged reserve rounded up to 16) */
+  uint64_t copy_pieces;        /* zd_k_multi_copy's grid: 32 KiB pieces of the staged reserves */
+  zd_batch_info2 batch;        /* the inner batch (zeroed for a batch of no chunks) */
+} zd_multi_info;
+/* The first `bytes` bytes of zd_multi_info (as zd_batch_info_get_sized); fewer
+ * than the six counters is ZD_E_INVALID_ARG. */
+int  zd_multi_info_get_sized(const zd_multi* m, zd_multi_info* info, size_t bytes);
+void zd_multi_destroy(zd_multi* m);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU: frame-range sharding + RCCL gather.      */

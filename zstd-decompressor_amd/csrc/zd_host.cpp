@@ -3151,12 +3151,16 @@ int zd_batch_bind_output(zd_batch* B, void* d_out, uint64_t cap) {
 
 int zd_chunk_sizes_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, size_t nchunks, uint32_t flags,
                           uint64_t* d_size, int32_t* d_status, uint8_t* d_exact, void* stream) {
-  if ((flags & ~(ZD_SIZES_DICT | ZD_SIZES_LONG_WINDOW | ZD_SIZES_RFC)) || nchunks >= (1ull << 31)) return ZD_E_INVALID_ARG;
+  if ((flags & ~(ZD_SIZES_DICT | ZD_SIZES_LONG_WINDOW | ZD_SIZES_RFC | ZD_SIZES_MULTI_FRAME)) || nchunks >= (1ull << 31))
+    return ZD_E_INVALID_ARG;
   if (nchunks && (!d_src_ptrs || !d_src_bytes || !d_size)) return ZD_E_INVALID_ARG;
   if (!nchunks) return ZD_OK;
-  HIPCHK(launch_chunk_sizes((const uint64_t*)d_src_ptrs, d_src_bytes, (uint32_t)nchunks,
-                            walk_opts((flags & ZD_SIZES_DICT) != 0, (flags & ZD_SIZES_LONG_WINDOW) != 0,
-                                      (flags & ZD_SIZES_RFC) != 0), d_size, d_status, d_exact, (hipStream_t)stream));
+  const uint32_t wopt = walk_opts((flags & ZD_SIZES_DICT) != 0, (flags & ZD_SIZES_LONG_WINDOW) != 0,
+                                  (flags & ZD_SIZES_RFC) != 0);
+  // (chunks of several frames: zd_multi.hip's kernel, the other one untouched)
+  HIPCHK((flags & ZD_SIZES_MULTI_FRAME ? launch_multi_sizes : launch_chunk_sizes)(
+      (const uint64_t*)d_src_ptrs, d_src_bytes, (uint32_t)nchunks, wopt, d_size, d_status, d_exact,
+      (hipStream_t)stream));
   return ZD_OK;
 }
 
@@ -3687,6 +3691,194 @@ int zd_seek_read_device_verdicts(const zd_seek_read* r, const uint32_t** d_entry
   if (d_ok) *d_ok = r->v_ok;
   if (d_hash32) *d_hash32 = r->v_hash32;
   if (n) *n = r->v_ok ? r->info.frames_decoded : 0;
+  return ZD_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Multi-frame batches (zd_multi_*): chunks of several concatenated zstd frames
+// as an ordinary device-built batch over their sub-chunks, whose chunk table
+// zd_multi.hip's kernels write, plus the pass that folds the sub-chunks'
+// results back into the chunks' and the one that delivers the staged bytes.
+// The rule is zd_multi.h's.
+// ===========================================================================
+namespace {
+constexpr uint32_t MULTI_FLAGS = SEEK_READ_FLAGS | ZD_F_RFC;
+}  // namespace
+
+struct zd_multi {
+  zd_batch* B = nullptr;                 // the sub-chunks; null: a batch of no chunks
+  int dev = -1;
+  uint8_t* d_mem = nullptr;              // one allocation for M's per-chunk arrays and the scan words
+  uint8_t* d_sub = nullptr;              // one for its per-sub-chunk arrays
+  MultiArrays M{};
+  uint8_t* d_stage = nullptr;            // the staged sub-chunks, from the workspace cache
+  uint64_t stage_alloc = 0;
+  uint64_t npieces = 0;
+  bool launched = false;
+  zd_multi_info info{};
+};
+
+extern "C" {
+
+void zd_multi_destroy(zd_multi* m) {
+  if (!m) return;
+  if (m->launched) (void)hipDeviceSynchronize();   // (the passes behind the batch's own work read the staging buffer)
+  if (m->B) zd_batch_destroy(m->B);
+  ws_release(m->d_stage, m->stage_alloc, m->dev);
+  if (m->d_mem) (void)hipFree(m->d_mem);
+  if (m->d_sub) (void)hipFree(m->d_sub);
+  delete m;
+}
+
+int zd_multi_create_device(const void* const* d_src_ptrs, const uint64_t* d_src_bytes, void* const* d_dst_ptrs,
+                           const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
+                           const zd_dict_set* set, void* stream, zd_multi** out) {
+  // ---- argument checks: no HIP call before they are done ----
+  if (!out || (flags & ZD_F_SKIPPABLE) || (flags & ~(MULTI_FLAGS | ZD_F_SKIPPABLE)) || nchunks >= (1ull << 31) ||
+      (dict && set))
+    return ZD_E_INVALID_ARG;
+  if (nchunks && (!d_src_ptrs || !d_src_bytes || !d_dst_ptrs || !d_dst_cap)) return ZD_E_INVALID_ARG;
+  BatchSpec S;
+  if (!spec_dicts(S, dict, set)) return ZD_E_INVALID_ARG;
+  struct DropMulti { void operator()(zd_multi* m) const { zd_multi_destroy(m); } };
+  std::unique_ptr<zd_multi, DropMulti> hold(new (std::nothrow) zd_multi());
+  zd_multi* m = hold.get();
+  if (!m) return ZD_E_NO_MEMORY;
+  m->info.nchunks = nchunks;
+  if (!nchunks) { *out = hold.release(); return ZD_OK; }
+  int dev = -1;
+  HIPCHK(hipGetDevice(&dev));
+  m->dev = dev;
+  const hipStream_t s = (hipStream_t)stream;
+  const uint32_t wopt = walk_opts(dict || set, (flags & ZD_F_LONG_WINDOW) != 0, (flags & ZD_F_RFC) != 0);
+  // ---- the per-chunk arrays ----
+  const uint64_t n = nchunks, n1 = n + 1, tiles = (n1 + 255) / 256;
+  uint64_t o = 0;
+  const auto take = [&](uint64_t bytes) { const uint64_t at = o; o += up16(bytes); return at; };
+  const uint64_t o_dst = take(8 * n), o_cap = take(8 * n), o_len = take(8 * n), o_first = take(4 * 8 * n1),
+                 o_tot = take(4 * 8 * (tiles + 1)), o_st = take(4 * n);
+  HIPCHK(hipMalloc(&m->d_mem, o));
+  HIPCHK(hipMemsetAsync(m->d_mem, 0, o, s));
+  MultiArrays& M = m->M;
+  uint8_t* b = m->d_mem;
+  M.dst = (uint64_t*)(b + o_dst); M.cap = (uint64_t*)(b + o_cap); M.len = (uint64_t*)(b + o_len);
+  M.first = (uint64_t*)(b + o_first); M.stage0 = M.first + n1; M.piece0c = M.first + 2 * n1;
+  M.nstaged = M.first + 3 * n1;
+  M.status = (int32_t*)(b + o_st);
+  M.n = (uint32_t)n;
+  // ---- the walk where the chunks lie, the scans; the one wait of this layer ----
+  const uint64_t *src = (const uint64_t*)d_src_ptrs, *dst = (const uint64_t*)d_dst_ptrs;
+  HIPCHK(launch_multi_count(src, d_src_bytes, dst, d_dst_cap, wopt, M, (uint64_t*)(b + o_tot), s));
+  uint64_t h[4] = {0, 0, 0, 0};
+  for (int c = 0; c < 4; c++)
+    HIPCHK(hipMemcpyAsync(h + c, M.first + c * n1 + n, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint64_t F = h[0], staged = h[1];
+  m->npieces = h[2];
+  m->info.frames = F;
+  m->info.staged_frames = h[3];
+  m->info.frames_in_place = F - h[3];
+  m->info.staged_bytes = staged;
+  m->info.copy_pieces = m->npieces;
+  if (F >= (1ull << 31) || m->npieces >= (1ull << 31)) return ZD_E_OUT_OF_DOMAIN;   // the inner batch; zd_k_multi_copy's grid
+  // ---- the per-sub-chunk arrays, the staging buffer, the chunk table, the inner batch ----
+  M.F = (uint32_t)F;
+  o = 0;
+  const uint64_t o_soff = take(8 * F), o_at = take(8 * F), o_piece = take(8 * (F + 1)), o_fdst = take(8 * F),
+                 o_chunk = take(4 * F);
+  HIPCHK(hipMalloc(&m->d_sub, o));
+  uint8_t* u = m->d_sub;
+  M.soff = (uint64_t*)(u + o_soff); M.at = (uint64_t*)(u + o_at); M.piece0 = (uint64_t*)(u + o_piece);
+  M.fdst = (uint64_t*)(u + o_fdst); M.chunk = (uint32_t*)(u + o_chunk);
+  HIPCHK(hipMemsetAsync(M.fdst, 0xFF, 8 * F, s));                 // (before the first join: nothing delivered)
+  if (staged) HIPCHK(ws_alloc(dev, staged, &m->d_stage, &m->stage_alloc));
+  uint64_t* cols = nullptr;
+  HIPCHK(hipMalloc(&cols, 4 * 8 * F));
+  std::unique_ptr<void, Free> cols_mem(cols);
+  HIPCHK(launch_multi_fill(src, d_src_bytes, dst, d_dst_cap, wopt, M, m->d_stage, cols, cols + F, cols + 2 * F,
+                           cols + 3 * F, s));
+  S.src = (const void* const*)cols; S.src_bytes = cols + F; S.dst = (void* const*)(cols + 2 * F); S.dst_cap = cols + 3 * F;
+  S.on_device = true; S.n = (size_t)F; S.flags = flags; S.stream = s;
+  if (int e = batch_create(S, &m->B)) return e;
+  (void)zd_batch_info_get_sized(m->B, &m->info.batch.info, sizeof(zd_batch_info2));
+  *out = hold.release();
+  return ZD_OK;
+}
+
+// the join and copy passes, behind the inner batch's work on s
+static int multi_passes(zd_multi* m, hipStream_t s) {
+  const int32_t* b_status = nullptr;
+  const uint64_t* b_len = nullptr;
+  (void)zd_batch_device_results(m->B, &b_status, &b_len);
+  HIPCHK(launch_multi_join(m->M, b_status, b_len, s));
+  HIPCHK(launch_multi_copy(m->M, m->d_stage, b_len, m->npieces, s));
+  return 0;
+}
+
+int zd_multi_decode_async(zd_multi* m, void* stream) {
+  if (!m) return ZD_E_INVALID_ARG;
+  if (!m->M.n) return ZD_OK;
+  if (int e = zd_batch_decode_async(m->B, stream)) return e;
+  if (int e = multi_passes(m, (hipStream_t)stream)) return e;
+  m->launched = true;
+  return ZD_OK;
+}
+
+int zd_multi_finish_async(zd_multi* m, void* stream) {
+  if (!m) return ZD_E_INVALID_ARG;
+  if (!m->M.n) return ZD_OK;
+  if (!m->launched) return ZD_E_INVALID_ARG;
+  return multi_passes(m, (hipStream_t)stream);
+}
+
+int zd_multi_device_results(const zd_multi* m, const int32_t** d_status, const uint64_t** d_len) {
+  if (!m) return ZD_E_INVALID_ARG;
+  if (d_status) *d_status = m->M.status;
+  if (d_len) *d_len = m->M.len;
+  return ZD_OK;
+}
+
+int zd_multi_device_frames(const zd_multi* m, const uint64_t** d_first, const int32_t** d_frame_status,
+                           const uint64_t** d_frame_len) {
+  if (!m) return ZD_E_INVALID_ARG;
+  const int32_t* b_status = nullptr;
+  const uint64_t* b_len = nullptr;
+  if (m->B) (void)zd_batch_device_results(m->B, &b_status, &b_len);
+  if (d_first) *d_first = m->M.first;
+  if (d_frame_status) *d_frame_status = b_status;
+  if (d_frame_len) *d_frame_len = b_len;
+  return ZD_OK;
+}
+
+int zd_multi_results(zd_multi* m, void* stream, int32_t* status, uint64_t* len, size_t cap, uint64_t* nfailed) {
+  if (!m || ((status || len) && cap < m->M.n)) return ZD_E_INVALID_ARG;
+  if (nfailed) *nfailed = 0;
+  const size_t n = m->M.n;
+  if (!n) return ZD_OK;
+  if (!m->launched) return ZD_E_INVALID_ARG;
+  const hipStream_t s = (hipStream_t)stream;
+  // (a K4J frame that did not converge is decoded again in there: its bytes and
+  // its sub-chunk's status are new, so the two passes run once more)
+  if (int e = zd_batch_results(m->B, stream, nullptr, nullptr, 0, nullptr)) return e;
+  if (int e = multi_passes(m, s)) return e;
+  HIPCHK(hipStreamSynchronize(s));
+  std::vector<int32_t> st(n);
+  HIPCHK(hipMemcpy(st.data(), m->M.status, 4 * n, hipMemcpyDeviceToHost));
+  if (len) HIPCHK(hipMemcpy(len, m->M.len, 8 * n, hipMemcpyDeviceToHost));
+  uint64_t bad = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (status) status[i] = st[i];
+    bad += st[i] != 0;
+  }
+  if (nfailed) *nfailed = bad;
+  return ZD_OK;
+}
+
+int zd_multi_info_get_sized(const zd_multi* m, zd_multi_info* info, size_t bytes) {
+  if (!m || !info || bytes < offsetof(zd_multi_info, batch)) return ZD_E_INVALID_ARG;
+  memcpy(info, &m->info, std::min(bytes, sizeof m->info));
   return ZD_OK;
 }
 

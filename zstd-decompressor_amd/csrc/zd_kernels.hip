@@ -6928,3 +6928,5 @@ hipError_t launch_batch_fit(HostFrame* frames, const HostBlock* blocks, const ui
 // The seekable-archive kernels (zd_k_seek_*), a file of their own compiled here:
 // libzd.so keeps one device code object.
 #include "zd_seek.hip"
+// The multi-frame batch's kernels (zd_k_multi_*), likewise.
+#include "zd_multi.hip"

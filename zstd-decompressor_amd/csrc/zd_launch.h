@@ -1,7 +1,8 @@
 // zd_launch.h — host-side entry points of the gfx950 kernels: launch_pipeline,
 // launch_reset, launch_dict_tables and launch_compact in zd_pipeline.hip, the
-// seekable layer's in zd_seek.hip, the others beside their kernels in
-// zd_kernels.hip (the one translation unit, which includes the two files).
+// seekable layer's in zd_seek.hip, the multi-frame batch's in zd_multi.hip,
+// the others beside their kernels in zd_kernels.hip (the one translation
+// unit, which includes the three files).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -299,6 +300,51 @@ hipError_t launch_seek_finish(const SeekRead& A, const uint64_t* d_off, const ui
 // a chunk of verdict 0 counts as ZD_E_CHECKSUM_WRONG.
 hipError_t launch_seek_results(const SeekRead& A, const uint64_t* d_off, const int32_t* b_status,
                                const uint64_t* b_len, const int8_t* v_ok, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// Multi-frame batches (zd_multi_*, zd_multi.hip; the rule: zd_multi.h)
+// ---------------------------------------------------------------------------
+// A multi-frame batch's device arrays: n chunks that hold F sub-chunks, each a
+// chunk of the inner batch.
+struct MultiArrays {
+  // per chunk
+  uint64_t *dst, *cap;         // the caller's destination (0 / 0 for a refused entry)
+  uint64_t* first;             // its first sub-chunk (exclusive scan; n + 1 entries, entry n = F)
+  uint64_t* stage0;            // its first staging byte         (first + (n + 1))
+  uint64_t* piece0c;           // its first 32 KiB copy piece    (first + 2 (n + 1))
+  uint64_t* nstaged;           // staged sub-chunks before it    (first + 3 (n + 1))
+  int32_t* status;             // the results
+  uint64_t* len;
+  // per sub-chunk (null until F is known)
+  uint32_t* chunk;             // the chunk it belongs to
+  uint64_t* soff;              // its staging offset, or MULTI_IN_PLACE
+  uint64_t* at;                // in place: its offset in the chunk's destination
+  uint64_t* piece0;            // its first copy piece (F + 1 entries)
+  uint64_t* fdst;              // staged: its final address (zd_k_multi_join), or MULTI_NOT_DELIVERED
+  uint32_t n, F;
+};
+// zd_k_multi_count (one lane a chunk: the header walk where the chunk lies) and
+// the scans of the four columns (tot: 4 x (tiles + 1) words, tiles of n + 1
+// entries); entry n of first / stage0 / piece0c / nstaged is then the total.
+hipError_t launch_multi_count(const uint64_t* src, const uint64_t* size, const uint64_t* dst, const uint64_t* cap,
+                              uint32_t wopt, const MultiArrays& M, uint64_t* tot, hipStream_t s);
+// zd_k_multi_fill: the inner batch's chunk table, four columns of F entries
+// (src, size, dst, cap), and the per-sub-chunk arrays; one lane a chunk.
+hipError_t launch_multi_fill(const uint64_t* src, const uint64_t* size, const uint64_t* dst, const uint64_t* cap,
+                             uint32_t wopt, const MultiArrays& M, uint8_t* staging, uint64_t* col_src,
+                             uint64_t* col_size, uint64_t* col_dst, uint64_t* col_cap, hipStream_t s);
+// zd_k_multi_join: the chunks' statuses and lengths from the inner batch's
+// (b_status / b_len, F entries), the staged sub-chunks' final addresses; one
+// lane a chunk.
+hipError_t launch_multi_join(const MultiArrays& M, const int32_t* b_status, const uint64_t* b_len, hipStream_t s);
+// zd_k_multi_copy: the delivered staged sub-chunks' decoded bytes to their final
+// addresses, one workgroup a 32 KiB piece of a staged reserve.
+hipError_t launch_multi_copy(const MultiArrays& M, const uint8_t* staging, const uint64_t* b_len, uint64_t npieces,
+                             hipStream_t s);
+// zd_k_multi_sizes: launch_chunk_sizes for chunks of several frames
+// (ZD_SIZES_MULTI_FRAME).
+hipError_t launch_multi_sizes(const uint64_t* src, const uint64_t* size, uint32_t n, uint32_t wopt, uint64_t* out_size,
+                              int32_t* status, uint8_t* exact, hipStream_t s);
 
 constexpr int N_KERNELS = 6;
 // mode-2 launch groups (LaunchArgs::dom_events: events 2g, 2g + 1)

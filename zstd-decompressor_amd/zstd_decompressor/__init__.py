@@ -10,7 +10,8 @@ Module map (reference -> here):
 Batch API (the hot path): batch.decompress / batch.Plan; batch.Batch for
 scattered device chunks with per-chunk buffers and statuses; batch.chunk_sizes /
 Batch.packed / batch.decompress_tensors when the decoded sizes are not known;
-seekable.SeekableArchive for byte ranges of a seekable archive on the device.
+seekable.SeekableArchive for byte ranges of a seekable archive on the device;
+multi.MultiFrameBatch / multi.decode_multi for chunks of several concatenated frames.
 """
 from . import _lib
 from ._lib import ZdError
@@ -21,8 +22,9 @@ from .decoding_context import DecodingContext
 from .batch import (Batch, Dictionary, DictionarySet, Plan, chunk_sizes, decode_tensors, decompress,
                     decompress_tensors, frames_index)
 from .seekable import SeekableArchive, SeekReader
+from .multi import MultiFrameBatch, decode_multi
 
 __all__ = ["ZdError", "ForwardByteParser", "Frame", "FrameIterator", "Header", "Skippable", "ZStandard",
            "MAX_WIN_SIZE", "Block", "DecodingContext", "Batch", "Dictionary", "DictionarySet",
            "Plan", "chunk_sizes", "decode_tensors", "decompress", "decompress_tensors",
-           "frames_index", "SeekableArchive", "SeekReader"]
+           "frames_index", "SeekableArchive", "SeekReader", "MultiFrameBatch", "decode_multi"]

@@ -91,6 +91,13 @@ class SeekReadInfo2(SeekReadInfo):
     _fields_ = [("read_flags", C.c_uint64), ("verify_entries", C.c_uint64)]
 
 
+class MultiInfo(C.Structure):
+    """zd_multi_info"""
+    _fields_ = [("nchunks", C.c_uint64), ("frames", C.c_uint64), ("frames_in_place", C.c_uint64),
+                ("staged_frames", C.c_uint64), ("staged_bytes", C.c_uint64), ("copy_pieces", C.c_uint64),
+                ("batch", BatchInfo2)]
+
+
 COMM_ID_BYTES = 128
 
 # every entry point declared in include/zd.h: name -> (restype, argtypes)
@@ -173,6 +180,15 @@ SIGNATURES = {
                                                C.POINTER(C.c_uint64)]),
     "zd_seek_read_info_get_sized": (C.c_int, [_vp, C.POINTER(SeekReadInfo), _sz]),
     "zd_seek_read_destroy": (None, [_vp]),
+    "zd_multi_create_device": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_uint32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "zd_multi_decode_async": (C.c_int, [_vp, _vp]),
+    "zd_multi_finish_async": (C.c_int, [_vp, _vp]),
+    "zd_multi_device_results": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "zd_multi_results": (C.c_int, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _sz,
+                                   C.POINTER(C.c_uint64)]),
+    "zd_multi_device_frames": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "zd_multi_info_get_sized": (C.c_int, [_vp, C.POINTER(MultiInfo), _sz]),
+    "zd_multi_destroy": (None, [_vp]),
     "zd_context_new": (C.c_int, [C.c_uint64, C.POINTER(_vp)]),
     "zd_context_free": (None, [_vp]),
     "zd_block_decode": (C.c_int, [_vp, _vp, _sz, _szp, C.POINTER(C.c_int)]),
@@ -320,5 +336,6 @@ SEEK_VERIFY_TABLE = 1  # zd_seekable_read_create_ex read_flags: the seek table's
 SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
 F_RFC = 16384           # frames decode as RFC 8878 / libzstd have them (default: the reference's decoder, D1-D3, D8)
 SIZES_RFC = 16384        # zd_chunk_sizes_device: the chunks will be decoded with F_RFC (the same bit)
+SIZES_MULTI_FRAME = 8    # zd_chunk_sizes_device: the chunks may hold several frames (a MultiFrameBatch will decode them)
 SIZES_LONG_WINDOW = 2048  # zd_chunk_sizes_device: the chunks will be decoded with F_LONG_WINDOW (the same bit)
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)

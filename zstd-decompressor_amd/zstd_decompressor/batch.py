@@ -304,7 +304,7 @@ def _device_arrays(arrs, nchunks, lists=True):
 
 
 def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, stream=None, long_window: bool = False,
-                rfc: bool = False):
+                rfc: bool = False, multi_frame: bool = False):
     """zd_chunk_sizes_device: what each chunk needs of its destination, asked
     on the device.  src_ptrs / src_sizes as in Batch.from_device (device
     tensors, or addresses with `nchunks`).  Returns three device tensors
@@ -314,7 +314,10 @@ def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, str
     its header walk.  dictionary=True when the chunks will be decoded with a
     Dictionary or DictionarySet, long_window=True when with F_LONG_WINDOW (a
     Window_Size up to 2 GiB is then no failure), rfc=True when with F_RFC (the
-    walk reads section headers as that flag does).  The kernel is queued on
+    walk reads section headers as that flag does), multi_frame=True when by a
+    MultiFrameBatch (a chunk may then hold several frames: the sum of its
+    sub-chunks' reserves, exact when all of them are, the first failing
+    sub-chunk's status).  The kernel is queued on
     `stream` (torch's current stream by default) and nothing is synchronised."""
     import torch
     if stream is None:
@@ -328,7 +331,8 @@ def chunk_sizes(src_ptrs, src_sizes, nchunks=None, dictionary: bool = False, str
     _lib.check(_lib.lib().zd_chunk_sizes_device(C.c_void_p(addr[0]), C.c_void_p(addr[1]), n,
                                                 (_lib.SIZES_DICT if dictionary else 0) |
                                                 (_lib.SIZES_LONG_WINDOW if long_window else 0) |
-                                                (_lib.SIZES_RFC if rfc else 0), ptr(sizes), ptr(statuses),
+                                                (_lib.SIZES_RFC if rfc else 0) |
+                                                (_lib.SIZES_MULTI_FRAME if multi_frame else 0), ptr(sizes), ptr(statuses),
                                                 ptr(exact), C.c_void_p(stream)), "zd_chunk_sizes_device")
     return sizes, statuses, exact
 
