@@ -2229,55 +2229,108 @@ __global__ __launch_bounds__(64) void zd_k_sequences_q(const uint8_t* __restrict
   const int lane = threadIdx.x;
   const int role = lane & 3, q = lane >> 2;
   const uint32_t li = blockIdx.x * K3Q_CHAINS + q;
-  bool act = q < K3Q_CHAINS && li < n_list;
-  const uint32_t ci = act ? list[li] : 0;
+  const bool act0 = q < K3Q_CHAINS && li < n_list;
+  bool act = act0;
+  const uint32_t ci = act0 ? list[li] : 0;
   CompBlock C;
-  if (act) C = comp[ci];
-  if (act && redo && !redo[C.frame]) act = false;   // the redo pass after zd_k_fused: flagged frames only
-  if (act) {
-    const uint64_t key0 = fstate[C.frame].key;
-    if (key0 != KEY_NONE && key_phase(key0) == PH_PARSE) act = false;
-  }
+  CompState cs;
   int al[3] = {0, 0, 0};
-  const uint16_t* g[3] = {nullptr, nullptr, nullptr};
-  if (act) {
+  uint32_t slot[3] = {0, 0, 0};                     // (slot 0 of an idle quad: readable, never stored)
+  if (act0) {
+    // Everything that hangs on the block's descriptor alone goes out
+    // together: the frame's key and redo flag, the block's own state and the
+    // three table sources' accuracy logs and slots.  (A listed block's
+    // tab_src are comp indices whatever its frame's key says: zd_plan.h.)
+    C = comp[ci];
+    const uint64_t key0 = fstate[C.frame].key;
+    cs = cstate[ci];
     for (int k = 0; k < 3; k++) {
       const uint32_t sidx = (uint32_t)C.tab_src[k];
       al[k] = cstate[sidx].al[k];
-      g[k] = fses + (uint64_t)comp[sidx].fse_slot * FSE_SLOT + k * FSE_TAB;
+      slot[k] = comp[sidx].fse_slot;
     }
+    if (redo && !redo[C.frame]) act = false;        // the redo pass after zd_k_fused: flagged frames only
+    if (key0 != KEY_NONE && key_phase(key0) == PH_PARSE) act = false;
   }
+  const uint16_t* g[3];
+  for (int k = 0; k < 3; k++) g[k] = fses + (uint64_t)slot[k] * FSE_SLOT + k * FSE_TAB;
   const bool deep = act && al[1] > 8;
   const bool use_lds = __ballot(deep) == 0;
   lds_u16* mine = (lds_u16*)tabs + q * K3_TAB;
-  if (use_lds && act) {
-    // the quad's lanes fill the three tables (lane k < 3: table k)
-    const int dst[3] = {0, K3_TL + K3_TM, K3_TL};     // LL | ML | OF in LDS
-    if (role < 3) {
-      const int k = role;
-      const int cnt = 1 << al[k];
-      if (cnt >= 8) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        typedef __attribute__((address_space(1))) const u32x4 g_u4;
-        typedef __attribute__((address_space(3))) u32x4 l_u4;
-        g_u4* s4 = (g_u4*)g[k];
-        l_u4* d4 = (l_u4*)(mine + dst[k]);
-        for (int e = 0; e < cnt / 8; e++) {
-          u32x4 v = s4[e];
-          v.x = K3_ENTRY(v.x & 0xFFFF, k, al[k]) | (K3_ENTRY(v.x >> 16, k, al[k]) << 16);
-          v.y = K3_ENTRY(v.y & 0xFFFF, k, al[k]) | (K3_ENTRY(v.y >> 16, k, al[k]) << 16);
-          v.z = K3_ENTRY(v.z & 0xFFFF, k, al[k]) | (K3_ENTRY(v.z >> 16, k, al[k]) << 16);
-          v.w = K3_ENTRY(v.w & 0xFFFF, k, al[k]) | (K3_ENTRY(v.w >> 16, k, al[k]) << 16);
-          d4[e] = v;
-        }
-      } else {
-        for (int e = 0; e < cnt; e++) mine[dst[k] + e] = (uint16_t)K3_ENTRY(((g_u16*)g[k])[e], k, al[k]);
+  if (use_lds) {
+    // The wave fills its quads' tables together, eight quads a round.  A
+    // 16-byte load a lane covers a whole 1 KiB slot table, so a round is
+    // 8 LL + 8 ML loads and 4 OF loads (OF is at most 256 entries here: two
+    // quads a load, a half-wave each), all issued before the first is used.
+    // Every lane loads, whatever the table's size or the quad's state -- the
+    // address is inside a slot either way -- and only the stores look at
+    // them, so no load sits behind a branch.  The table kind is fixed per
+    // load and the accuracy log comes from the quad's lanes by readlane, so
+    // the entries convert without the role switch.
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) const u32x4 g_u4;
+    typedef __attribute__((address_space(3))) u32x4 l_u4;
+    constexpr int QR = 8;                            // quads a round
+    // al LL | OF << 8 | ML << 16 | active << 24 (0: the quad stores nothing)
+    const uint32_t desc = act ? (uint32_t)al[0] | (uint32_t)al[1] << 8 | (uint32_t)al[2] << 16 | 1u << 24 : 0u;
+    auto conv = [](u32x4 v, int k, int a) -> u32x4 {
+      v.x = K3_ENTRY(v.x & 0xFFFF, k, a) | (K3_ENTRY(v.x >> 16, k, a) << 16);
+      v.y = K3_ENTRY(v.y & 0xFFFF, k, a) | (K3_ENTRY(v.y >> 16, k, a) << 16);
+      v.z = K3_ENTRY(v.z & 0xFFFF, k, a) | (K3_ENTRY(v.z >> 16, k, a) << 16);
+      v.w = K3_ENTRY(v.w & 0xFFFF, k, a) | (K3_ENTRY(v.w >> 16, k, a) << 16);
+      return v;
+    };
+    const int hl = lane >> 5, l32 = lane & 31;      // OF: the lane's half-wave and place in it
+#pragma unroll 1
+    for (int h = 0; h < K3Q_CHAINS; h += QR) {
+      u32x4 vl[QR], vm[QR], vo[QR / 2];
+#pragma unroll
+      for (int j = 0; j < QR; j++) {
+        const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane((int)slot[0], 4 * (h + j));
+        const uint32_t s2 = (uint32_t)__builtin_amdgcn_readlane((int)slot[2], 4 * (h + j));
+        vl[j] = ((g_u4*)(fses + (uint64_t)s0 * FSE_SLOT))[lane];
+        vm[j] = ((g_u4*)(fses + (uint64_t)s2 * FSE_SLOT + 2 * FSE_TAB))[lane];
       }
+#pragma unroll
+      for (int j = 0; j < QR; j += 2) {
+        const uint32_t sa = (uint32_t)__builtin_amdgcn_readlane((int)slot[1], 4 * (h + j));
+        const uint32_t sb = (uint32_t)__builtin_amdgcn_readlane((int)slot[1], 4 * (h + j + 1));
+        vo[j / 2] = ((g_u4*)(fses + (uint64_t)(hl ? sb : sa) * FSE_SLOT + FSE_TAB))[l32];
+      }
+      // (the first table's use, pinned here: the compiler otherwise sinks its
+      // load into the branch of its store and drains the whole round there)
+      asm volatile("" : "+v"(vl[0]));
+#pragma unroll
+      for (int j = 0; j < QR; j++) {
+        const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)desc, 4 * (h + j));
+        const int a0 = d & 255, a2 = (d >> 16) & 255;
+        const int on = d >> 24;
+        lds_u16* t = (lds_u16*)tabs + (h + j) * K3_TAB;
+        // (tables of fewer than 8 entries: below)
+        if (on && a0 >= 3 && 8 * lane < (1 << a0)) ((l_u4*)t)[lane] = conv(vl[j], 0, a0);
+        if (on && a2 >= 3 && 8 * lane < (1 << a2)) ((l_u4*)(t + K3_TL))[lane] = conv(vm[j], 2, a2);
+      }
+#pragma unroll
+      for (int j = 0; j < QR; j += 2) {
+        const uint32_t da = (uint32_t)__builtin_amdgcn_readlane((int)desc, 4 * (h + j));
+        const uint32_t db = (uint32_t)__builtin_amdgcn_readlane((int)desc, 4 * (h + j + 1));
+        const uint32_t d = hl ? db : da;
+        const int a1 = (d >> 8) & 255;
+        lds_u16* t = (lds_u16*)tabs + (h + j + hl) * K3_TAB + K3_TL + K3_TM;
+        if ((d >> 24) && a1 >= 3 && 8 * l32 < (1 << a1)) ((l_u4*)t)[l32] = conv(vo[j / 2], 1, a1);
+      }
+    }
+    // a table of fewer than 8 entries (RLE mode's one): lane k < 3 of the
+    // quad stores table k's entries one by one
+    const int ar = role == 0 ? al[0] : role == 1 ? al[1] : al[2];
+    if (act && role < 3 && ar < 3) {
+      const int dst = role == 0 ? 0 : role == 1 ? K3_TL + K3_TM : K3_TL;      // LL | ML | OF in LDS
+      const g_u16* gr = (g_u16*)(role == 0 ? g[0] : role == 1 ? g[1] : g[2]);
+      for (int e = 0; e < (1 << ar); e++) mine[dst + e] = (uint16_t)K3_ENTRY(gr[e], role, ar);
     }
   }
   __syncthreads();
   if (!act) return;
-  const CompState cs = cstate[ci];
   const uint8_t* blk = src + C.src;
   const uintptr_t lo = (uintptr_t)src;
   int st = 0;
