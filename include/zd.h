@@ -159,7 +159,8 @@ typedef struct zd_plan zd_plan;
  * automatic.  Same output either way; tests run both.  Plans with a
  * dictionary or a dictionary set, chain batches and zd_context ignore both
  * flags (the streaming executor only; a chain batch has a flag of its own,
- * ZD_F_CHAIN_BLOCK_PARALLEL); a prefix batch (zd_batch_create_prefix,
+ * ZD_F_CHAIN_BLOCK_PARALLEL, and so have dictionary plans,
+ * ZD_F_DICT_BLOCK_PARALLEL, under which the two flags mean what they say); a prefix batch (zd_batch_create_prefix,
  * zd_batch_create_device_prefix) ignores the plain plans' automatic rule and
  * takes K4J when ZD_F_BLOCK_PARALLEL asks for it -- large deltas, whose
  * hundreds of blocks one wave would decode one after another -- or chunk by
@@ -323,6 +324,50 @@ typedef struct zd_plan zd_plan;
  * zd_context / zd_block_decode / zd_execute_sequences take no flags and stay
  * the reference's.  Without the flag nothing changes. */
 #define ZD_F_RFC 16384u
+/* Dictionary and dictionary-set plans and batches on the block-parallel
+ * executor (opt-in).  Without this flag every frame behind a dictionary runs on
+ * the streaming executor, one wave a frame, block after block, and
+ * ZD_F_BLOCK_PARALLEL and ZD_F_AUTO_EXECUTOR mean nothing there.  With it --
+ * in zd_plan_create_dict / _dicts, zd_decompress_dict / _dicts,
+ * zd_batch_create_dicts, zd_batch_create_device_dicts,
+ * zd_batch_create_device_packed_dicts and a multi-frame batch with a
+ * dictionary or set (zd_multi_create_device hands the flag to its inner batch;
+ * without a dictionary it refuses the bit, as it refuses every flag that is
+ * not its own) -- a frame may execute
+ * on K4J when it is a zstd frame that did not fail to index, has a compressed
+ * block, a capacity within K4J's 32 GiB and dictionary content of at most
+ * 0x7FFF0000 bytes:
+ *  - with ZD_F_FRAME_SERIAL no frame goes to K4J;
+ *  - with ZD_F_BLOCK_PARALLEL every such frame does;
+ *  - with neither, each such frame is routed by ZD_F_AUTO_EXECUTOR's rule with
+ *    the ZD_AUTO_* constants above: (a) with the plan's frame count (a batch's
+ *    chunk count) as the width and the candidates counted over the whole plan,
+ *    against ZD_AUTO_DICT_MAX_CANDIDATES in ZD_AUTO_MAX_CANDIDATES' place,
+ *    (b) dictionary content plus capacity past 0x7FFF0000 while the content
+ *    alone fits.  The three other constants were measured on prefix batches
+ *    (the same scatter path) and are kept for dictionary plans; the cap is the
+ *    one that scripts/time_dict_big.py's grid moved (EXPERIMENTS.md).
+ * A frame of a set plan that decodes without a dictionary is routed alike (its
+ * source is 0 bytes).  Frames of raw / RLE blocks only stay where they are; the
+ * fused kernel and K4F stay off.  K4J's scatter writes the bytes that come from
+ * the dictionary; an offset past the content plus the position is
+ * ZD_E_IMPOSSIBLE_VALUE as on the streaming executor.  A frame whose pointer
+ * jumping does not converge is decoded again on the streaming executor with its
+ * dictionary or set: inside zd_batch_results for a batch (zd_batch_device_results
+ * shows ZD_E_OUT_OF_DOMAIN until then), by zd_plan_decompress's re-plan for a
+ * plan.  zd_plan_info.executors / zd_batch_info.executors carry ZD_EXEC_K4J only
+ * when a frame went there; zd_batch_info2.k4j_chunks counts them.  The same
+ * bytes, statuses and lengths as without the flag, but for (b).
+ * Everywhere else the flag is accepted and ignored: plain plans and batches,
+ * prefix and chain batches, the sharded calls.  A seekable read has no
+ * dictionary and refuses the bit in its plan flags (ZD_E_INVALID_ARG).  Without
+ * the flag nothing changes. */
+#define ZD_F_DICT_BLOCK_PARALLEL 32768u
+#define ZD_AUTO_DICT_MAX_CANDIDATES 192  /* (a) in a dictionary plan holds only while at most this many frames meet it:
+                                            frames behind a dictionary are whole text frames, not deltas, and K4J's
+                                            time grows faster with them (192 frames of 16 blocks 10.3 ms against 11.3
+                                            streaming, of 4 blocks 3.57 against 3.72; 256 frames 13.2 against 11.3 and
+                                            4.32 against 3.69) */
 
 /* zd_plan_info.executors: */
 #define ZD_EXEC_FUSED 1u   /* zd_k_fused: tables, FSE chains and execution per group of four
@@ -523,7 +568,8 @@ int  zd_dict_info(const zd_dict* d, uint32_t* dict_id, uint64_t* content_size,
  * every zd_plan_* call and zd_decode_async work as on any plan (no host copy
  * or allocation per launch; capturable).  A dictionary made on another
  * device: ZD_E_INVALID_ARG.
- * Limits: dictionary plans run on the streaming executor only -- never the
+ * Limits: without ZD_F_DICT_BLOCK_PARALLEL (see the flag) dictionary plans run
+ * on the streaming executor only -- never the
  * fused kernel, K4F or K4J, ZD_F_BLOCK_PARALLEL is ignored and
  * zd_plan_info.executors is 0; a frame whose dictionary content plus
  * capacity passes the streaming executor's int32 positions is
@@ -578,7 +624,8 @@ int  zd_dict_set_info(const zd_dict_set* set, size_t* ndicts, int* fallback);
  * with fallback 0 gives the bytes and statuses of zd_plan_create_dict.  A frame
  * that zd_plan_decompress plans again (capacity) keeps its own dictionary.
  * Limits, as in zd_plan_create_dict and for every frame of the plan, the ones
- * without a dictionary included: the streaming executor only -- never the
+ * without a dictionary included: without ZD_F_DICT_BLOCK_PARALLEL the streaming
+ * executor only -- never the
  * fused kernel, K4F or K4J, ZD_F_BLOCK_PARALLEL is ignored and
  * zd_plan_info.executors is 0; a frame whose own dictionary's content plus
  * capacity passes the streaming executor's int32 positions is
@@ -658,7 +705,8 @@ typedef struct zd_batch_info2 {
  * host.  Synchronises `stream`.
  * flags: the executor and chain flags of a plan, with a plan's routing;
  * ZD_F_SKIPPABLE is ZD_E_INVALID_ARG.  dict (may be NULL): every chunk decodes
- * with it, under zd_plan_create_dict's limits (the streaming executor only).
+ * with it, under zd_plan_create_dict's limits (the streaming executor only,
+ * unless flags has ZD_F_DICT_BLOCK_PARALLEL).
  * ZD_E_INVALID_ARG, before any HIP call: a NULL array with nchunks > 0, a NULL
  * d_src[i] with src_bytes[i] > 0, a NULL d_dst[i] with dst_cap[i] > 0,
  * destination ranges that overlap. */

@@ -464,8 +464,12 @@ struct JFrame {
   uint64_t piece0;         // first 16-byte piece of the frame in the rounds' piece numbering
   uint32_t frame;          // plan frame index
   uint32_t jb0, njb;       // its blocks: JBlkDesc / JBlk [jb0, jb0 + njb)
-  uint32_t pad;
+  // a dictionary plan's J frame (ZD_F_DICT_BLOCK_PARALLEL): its dictionary's entry in the scatter's table of
+  // content addresses -- 0 with one dictionary, Sink::frame_dict's value in a set plan; 0 and unread elsewhere
+  // (the four bytes were padding)
+  uint32_t src;
 };
+static_assert(sizeof(JFrame) == 40, "JFrame: src lies in what was padding");
 struct JBlkDesc {          // static, from the host
   uint32_t block;          // BlockRec index
   uint32_t jframe;         // JFrame index

@@ -78,6 +78,10 @@ struct DictData {
   uint16_t* d_lut = nullptr;             // formatted: one LUT slot (the pair table) and one FSE slot
   uint16_t* d_fse = nullptr;
   uint8_t huf_bits = 0, al[3] = {0, 0, 0};
+  // d_content in device memory, eight bytes at the end of d_buf: the one-entry table of content addresses that
+  // K4J's scatter reads in a zd_plan_create_dict plan created with ZD_F_DICT_BLOCK_PARALLEL (a set plan has its
+  // workspace's table)
+  const uint8_t** d_self = nullptr;
   ~DictData() {
     if (d_buf) (void)hipFree(d_buf);
     if (d_lut) (void)hipFree(d_lut);
@@ -173,7 +177,9 @@ struct zd_plan {
     if (chain) { w = 0; for (uint32_t c : chain_count) w = std::max<uint64_t>(w, c); }
     return w;
   }
-  uint32_t k4j_min() const { return plan_k4j_min(flags, prefix, chain, nframes, auto_width()); }
+  // a dictionary or dictionary-set plan created with ZD_F_DICT_BLOCK_PARALLEL (zd_route.h dict_j)
+  bool dict_j() const { return zd::dict_j(flags, (dict != nullptr || dset != nullptr) && !prefix); }
+  uint32_t k4j_min() const { return plan_k4j_min(flags, prefix, chain, nframes, auto_width(), dict_j()); }
   uint32_t jpend_words() const {
     return chain_on_j() ? jpend_chain_words((uint32_t)chain_count.size()) : JPEND_WORDS;
   }
@@ -444,7 +450,7 @@ PlanCtx plan_ctx(const zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], 
   X.fused = r.fused;
   X.k4f_on = r.k4f;
   plan_k4j_fields(X, P->flags, route_env(), X.dict, P->prefix, P->chain, out_len0, P->nframes, P->auto_width(),
-                  j_candidates);
+                  j_candidates, P->dict_j());
   return X;
 }
 
@@ -601,7 +607,7 @@ int build_plan(zd_plan* P, int32_t prev_huf, const int32_t prev_tab[3], uint64_t
                const uint64_t rep0[3], uint64_t fixed_cap, bool staged = false) {
   P->cus = device_cus();
   uint64_t j_candidates = 0;
-  if (plan_k4j_counts(P->flags, route_env(), P->prefix, P->chain, out_len0)) {
+  if (plan_k4j_counts(P->flags, route_env(), P->prefix, P->chain, out_len0, P->dict_j())) {
     const uint32_t k4j_min = P->k4j_min();
     for (const HostPart& hp : P->parts)
       for (const HostFrame& hf : hp.frames) j_candidates += hf.key == KEY_NONE && hf.ncomp >= k4j_min;
@@ -1386,8 +1392,9 @@ int build_plan_device(zd_plan* P, DevWalkBufs& B, uint64_t F, hipStream_t s, Dev
   if (P->with_dict()) plan_dict_comps(P, used.data());
   const DictData* D = P->dict.get();
   const bool tabs = D && !D->raw;
+  const bool counts = plan_k4j_counts(P->flags, route_env(), P->prefix, P->chain, 0, P->dict_j());
   PlanCtx X = plan_ctx(P, tabs ? 0 : -1, tabs ? pre : none, D ? D->content : 0, D ? D->rep : rep0, 0, shape.multi == 0,
-                       plan_k4j_counts(P->flags, route_env(), P->prefix, P->chain, 0) ? shape.jcand : 0);
+                       counts ? shape.jcand : 0);
   if (in) { X.place_out = in->place_out; X.place_cap = in->place_cap; }
   if (P->dset) {
     if (!in || !in->d_dset) return ZD_E_INVALID_ARG;
@@ -2013,7 +2020,7 @@ static int decode_launch(zd_plan* P, const uint8_t* d_src, uint8_t* out, hipStre
   a.aux = P->aux; a.fork = P->fork; a.join = P->join;
   a.events = P->ev; a.dom_events = P->dom_ev; a.dom_used = &P->dom_used;
   P->dom_used = 0;
-  if (P->dict) a.dict = P->dict->d_content;
+  if (P->dict) { a.dict = P->dict->d_content; a.dict_tab = P->dict->d_self; }
   P->last_fused = R.fused;
   if (R.fused) {
     HIPCHK(hipMemsetAsync(P->d_ws + P->W.redo, 0, std::max<uint64_t>(P->n_frames, 1), s));
@@ -2368,8 +2375,8 @@ int zd_dict_create(const uint8_t* dict, size_t n, zd_dict** out) {
   if (!D || !h) { delete h; return ZD_E_NO_MEMORY; }
   std::unique_ptr<zd_dict> hold(h);
   HIPCHK(hipGetDevice(&D->dev));
-  const size_t bytes = DICT_PAD + n + 2 * DICT_PAD;
-  HIPCHK(hipMalloc(&D->d_buf, bytes));
+  const size_t bytes = DICT_PAD + n + 2 * DICT_PAD, self_at = (bytes + 7) & ~(size_t)7;
+  HIPCHK(hipMalloc(&D->d_buf, self_at + sizeof(const uint8_t*)));
   HIPCHK(hipMemset(D->d_buf, 0, DICT_PAD));
   HIPCHK(hipMemset(D->d_buf + DICT_PAD + n, 0, 2 * DICT_PAD));
   HIPCHK(hipMemcpy(D->d_buf + DICT_PAD, dict, n, hipMemcpyHostToDevice));
@@ -2405,6 +2412,8 @@ int zd_dict_create(const uint8_t* dict, size_t n, zd_dict** out) {
     D->huf_bits = (uint8_t)res.huf_bits;
     for (int k = 0; k < 3; k++) D->al[k] = res.al[k];
   }
+  D->d_self = (const uint8_t**)(D->d_buf + self_at);
+  HIPCHK(hipMemcpy(D->d_self, &D->d_content, sizeof(const uint8_t*), hipMemcpyHostToDevice));
   h->p = std::move(D);
   *out = hold.release();
   return ZD_OK;
@@ -3287,8 +3296,10 @@ int zd_batch_results(zd_batch* B, void* stream, int32_t* status, uint64_t* len, 
       // a prefix batch (K4J only with ZD_F_BLOCK_PARALLEL or ZD_F_AUTO_EXECUTOR): the redo chunks'
       // checked prefix addresses and sizes go with them -- a chunk whose prefix
       // plus capacity the streaming executor cannot hold ends ZD_E_OUT_OF_DOMAIN.
-      // (plan_ctx turns K4J off for every dictionary and set plan, so such a
-      // batch never has n_jframes; a chain batch: the roots' entries only)
+      // (a chain batch: the roots' entries only.  A dictionary or set batch has
+      // n_jframes only with ZD_F_DICT_BLOCK_PARALLEL: its redo batch takes the
+      // dictionary or set below and ZD_F_FRAME_SERIAL, which keeps every frame
+      // on the streaming executor whatever else the flags say)
       std::vector<const void*> pf;
       std::vector<uint64_t> pz;
       if (P->prefix) {
@@ -3705,6 +3716,9 @@ int zd_seek_read_device_verdicts(const zd_seek_read* r, const uint32_t** d_entry
 // ===========================================================================
 namespace {
 constexpr uint32_t MULTI_FLAGS = SEEK_READ_FLAGS | ZD_F_RFC;
+// (with a dictionary or set only, where it means something: the inner batch gets it; without one it stays an
+// unknown bit, as it was)
+constexpr uint32_t MULTI_DICT_FLAGS = ZD_F_DICT_BLOCK_PARALLEL;
 }  // namespace
 
 struct zd_multi {
@@ -3736,7 +3750,8 @@ int zd_multi_create_device(const void* const* d_src_ptrs, const uint64_t* d_src_
                            const uint64_t* d_dst_cap, size_t nchunks, uint32_t flags, const zd_dict* dict,
                            const zd_dict_set* set, void* stream, zd_multi** out) {
   // ---- argument checks: no HIP call before they are done ----
-  if (!out || (flags & ZD_F_SKIPPABLE) || (flags & ~(MULTI_FLAGS | ZD_F_SKIPPABLE)) || nchunks >= (1ull << 31) ||
+  if (!out || (flags & ZD_F_SKIPPABLE) ||
+      (flags & ~(MULTI_FLAGS | ZD_F_SKIPPABLE | (dict || set ? MULTI_DICT_FLAGS : 0u))) || nchunks >= (1ull << 31) ||
       (dict && set))
     return ZD_E_INVALID_ARG;
   if (nchunks && (!d_src_ptrs || !d_src_bytes || !d_dst_ptrs || !d_dst_cap)) return ZD_E_INVALID_ARG;

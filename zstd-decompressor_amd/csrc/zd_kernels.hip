@@ -5472,7 +5472,17 @@ __device__ __attribute__((always_inline)) inline uint32_t j_match_word(uint32_t 
 // planned with, keys the frame ZD_E_NOT_DECODED (key_min, the streaming
 // kernel's key), and the wave writes no word; zd_k_jround skips a keyed frame.
 // Without CHAIN the two arguments after pfx_ptrs are never read.
-template <bool PFX, bool CHAIN = false>
+// DICT (a dictionary or dictionary-set plan created with
+// ZD_F_DICT_BLOCK_PARALLEL; with PFX, never with CHAIN): the bytes before the
+// frame's first are its dictionary's content, pfx_ptrs[JFrame::src] of
+// frames[f].out_len0 bytes -- pfx_ptrs is the plan's table of content addresses
+// (one entry for zd_plan_create_dict, Workspace::dict_ptrs for a set, whose
+// last entry serves the frames without a dictionary: out_len0 = 0, never read).
+// The reads are the prefix frames': inside [pfx, pfx + out_len0), a whole piece
+// inside one match by one 16-byte load of any alignment (two aligned loads and
+// a funnel shift in its place read no fewer lines).  The other instantiations
+// keep their instructions.
+template <bool PFX, bool CHAIN = false, bool DICT = false>
 __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ src, FrameState* fstate,
                                                     const BlockRec* __restrict__ blocks,
                                                     const CompBlock* __restrict__ comp,
@@ -5519,7 +5529,8 @@ __global__ __launch_bounds__(64) void zd_k_jscatter(const uint8_t* __restrict__ 
   const uint8_t* pfx = nullptr;
   uint32_t P = 0;
   if constexpr (PFX) {
-    pfx = pfx_ptrs[JF.frame];
+    static_assert(!DICT || !CHAIN, "a dictionary plan is no chain batch");
+    pfx = pfx_ptrs[DICT ? JF.src : JF.frame];
     P = (uint32_t)frames[JF.frame].out_len0;
   }
   const CompBlock C = comp[B.comp];

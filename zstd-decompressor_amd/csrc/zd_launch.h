@@ -42,6 +42,10 @@ struct LaunchArgs {
   // (Workspace::dict_ptrs, ::frame_dict), a prefix batch (K4_PREFIX) frame f's
   // prefix from dict_ptrs[f]
   const uint8_t* dict = nullptr;
+  // K4_DICT with K4J frames (ZD_F_DICT_BLOCK_PARALLEL): that address in device
+  // memory, the one-entry table zd_k_jscatter reads through JFrame::src (a set
+  // plan's table is Workspace::dict_ptrs)
+  const uint8_t* const* dict_tab = nullptr;
   // route.k4 == K4_CHAIN (zd_batch_create_chain): the frames grouped by level
   // (device, n_frames entries), each frame's parent (device, -1: none) and the
   // levels' frame counts (host, chain_levels entries; level l's frames are

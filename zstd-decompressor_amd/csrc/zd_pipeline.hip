@@ -186,13 +186,16 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
   // the frames read prefixes (the scatter gets no frames / dict_ptrs
   // otherwise).  lvl: the range is one level of a chain batch -- the scatter
   // checks the frames' parents, and a level without a piece gets no round (a
-  // whole plan's rounds are launched whatever a.j_pieces is).
-  auto k4j_range = [&](auto pfx_c, auto lvl_c, hipStream_t st, uint32_t seg0, uint32_t nseg, uint32_t jf0,
-                       uint64_t pieces, uint32_t* pend) {
-    constexpr bool pfx = decltype(pfx_c)::value, lvl = decltype(lvl_c)::value;
-    hipLaunchKernelGGL((zd_k_jscatter<pfx, lvl>), dim3(nseg), dim3(64), 0, st, a.src, w.fstate, w.blocks, w.comp,
+  // whole plan's rounds are launched whatever a.j_pieces is).  dct (with pfx):
+  // a dictionary or dictionary-set plan -- the scatter's table holds the plan's
+  // dictionaries' content addresses, src_tab (one entry, LaunchArgs::dict_tab,
+  // or the workspace's table of a set), not the frames' prefixes.
+  auto k4j_range = [&](auto pfx_c, auto lvl_c, auto dct_c, hipStream_t st, uint32_t seg0, uint32_t nseg, uint32_t jf0,
+                       uint64_t pieces, uint32_t* pend, const uint8_t* const* src_tab) {
+    constexpr bool pfx = decltype(pfx_c)::value, lvl = decltype(lvl_c)::value, dct = decltype(dct_c)::value;
+    hipLaunchKernelGGL((zd_k_jscatter<pfx, lvl, dct>), dim3(nseg), dim3(64), 0, st, a.src, w.fstate, w.blocks, w.comp,
                        w.cstate, w.lits, w.seqs, w.fses, w.jframes, w.jd, w.jb, w.jseg, w.jsd, w.jst,
-                       pfx ? w.frames : nullptr, pfx ? w.dict_ptrs : nullptr, seg0, lvl ? a.chain_parent : nullptr);
+                       pfx ? w.frames : nullptr, pfx ? src_tab : nullptr, seg0, lvl ? a.chain_parent : nullptr);
     const dim3 gr = j_grid(pieces, a.cus);
     // round 1 one launch, the rest as one launch of sweeps
     // (one launch of all the sweeps: 1.43 ms for the rounds of c3s, against
@@ -227,8 +230,8 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
         if (!cj || !a.chain_j[l].njf) continue;
         // (the level's own pend slots, 3 a level: rounds 1 and 2 use [1] and [2])
         const JLevel& L = a.chain_j[l];
-        k4j_range(std::true_type{}, std::true_type{}, s, (uint32_t)L.seg0, (uint32_t)L.nseg, (uint32_t)L.jf0,
-                  L.npieces, w.jpend + 3 * l);
+        k4j_range(std::true_type{}, std::true_type{}, std::false_type{}, s, (uint32_t)L.seg0, (uint32_t)L.nseg,
+                  (uint32_t)L.jf0, L.npieces, w.jpend + 3 * l, w.dict_ptrs);
       }
       if (n && k4_work) if ((e = dom(DOM_K4, 1)) != hipSuccess) return e;
       return hipSuccess;
@@ -283,9 +286,15 @@ hipError_t launch_pipeline(const LaunchArgs& a) {
     if ((e = dom(DOM_K4J, 0)) != hipSuccess) return e;
     k4j_tables(s);
     if (R.k4 == K4_PREFIX)                     // each frame's own prefix, as the streaming launch above reads it
-      k4j_range(std::true_type{}, std::false_type{}, s, 0u, a.n_jseg, 0u, a.j_pieces, w.jpend);
-    else
-      k4j_range(std::false_type{}, std::false_type{}, s, 0u, a.n_jseg, 0u, a.j_pieces, w.jpend);
+      k4j_range(std::true_type{}, std::false_type{}, std::false_type{}, s, 0u, a.n_jseg, 0u, a.j_pieces, w.jpend,
+                w.dict_ptrs);
+    else if (R.k4 == K4_DICT || R.k4 == K4_DICT_SET) {   // ZD_F_DICT_BLOCK_PARALLEL: the dictionary, or each frame's own
+      const uint8_t* const* tab = R.k4 == K4_DICT ? a.dict_tab : w.dict_ptrs;
+      if (!tab) return hipErrorInvalidValue;   // (never: zd_dict_create makes the one-entry table)
+      k4j_range(std::true_type{}, std::false_type{}, std::true_type{}, s, 0u, a.n_jseg, 0u, a.j_pieces, w.jpend, tab);
+    } else
+      k4j_range(std::false_type{}, std::false_type{}, std::false_type{}, s, 0u, a.n_jseg, 0u, a.j_pieces, w.jpend,
+                nullptr);
     if ((e = dom(DOM_K4J, 1)) != hipSuccess) return e;
   }
   if ((e = ev(6)) != hipSuccess) return e;

@@ -92,6 +92,15 @@ struct PlanCtx {
   // frame's own bytes).  dict_id: the dictionary's ID (0: raw content).
   bool dict;
   uint32_t dict_id;
+  // A dictionary or dictionary-set plan created with ZD_F_DICT_BLOCK_PARALLEL
+  // (zd_route.h dict_j; false everywhere else, and never with prefix_bytes):
+  // a frame with a compressed block may go to K4J behind its dictionary -- all
+  // of them with k4j_mode 1, with auto_exec those plan_auto_j names (k4j_min
+  // the rule's minimum at the plan's frame count, k4j_auto its candidates
+  // within the cap), none with neither.  Such a J frame keeps out_len0, the
+  // repeat offsets and the previous tables of its dictionary (the plan-wide
+  // fields, or its own PlanDict entry), and JFrame::src names the entry.
+  bool dict_j;
   // Optional per-frame placement (a batch; null everywhere else): host arrays
   // in the host planner (zd_batch_create), device arrays in the device planner
   // (zd_batch_create_device).  Frame fi's output starts at
@@ -137,24 +146,36 @@ struct PlanCtx {
 // elsewhere).  plan_k4j_min is known before the walk's frames are looked at;
 // `candidates` are the frames without a walk-found error and with at least that
 // many compressed blocks, counted where plan_k4j_counts says a rule reads them.
-inline uint32_t plan_k4j_min(uint32_t flags, bool prefix, bool chain, uint64_t nframes, uint64_t width) {
-  return auto_exec(flags, prefix, chain) ? auto_min_blocks(width)
+inline uint32_t plan_k4j_min(uint32_t flags, bool prefix, bool chain, uint64_t nframes, uint64_t width,
+                             bool dict_j = false) {
+  return auto_exec(flags, prefix, chain) || dict_j ? auto_min_blocks(width)
          : nframes <= K4J_FEW_FRAMES    ? K4J_MIN_BLOCKS_FEW
                                         : K4J_MIN_BLOCKS;
 }
-inline bool plan_k4j_counts(uint32_t flags, const RouteEnv& E, bool prefix, bool chain, uint64_t out_len0) {
+inline bool plan_k4j_counts(uint32_t flags, const RouteEnv& E, bool prefix, bool chain, uint64_t out_len0,
+                            bool dict_j = false) {
+  if (dict_j) return dict_j_mode(flags) < 0;
   return auto_exec(flags, prefix, chain) || (k4j_mode_of(flags, E) < 0 && out_len0 == 0);
 }
 inline void plan_k4j_fields(PlanCtx& X, uint32_t flags, const RouteEnv& E, bool dict, bool prefix, bool chain,
-                            uint64_t out_len0, uint64_t nframes, uint64_t width, uint64_t candidates) {
+                            uint64_t out_len0, uint64_t nframes, uint64_t width, uint64_t candidates,
+                            bool dict_j = false) {
+  X.dict_j = dict_j;
   X.k4j_mode = k4j_mode_of(flags, E);
-  X.k4j_min = plan_k4j_min(flags, prefix, chain, nframes, width);
+  X.k4j_min = plan_k4j_min(flags, prefix, chain, nframes, width, dict_j);
   X.k4j_auto = X.k4j_mode < 0 && out_len0 == 0 && candidates > 0 && candidates <= K4J_MAX_FRAMES;
   X.auto_exec = false;
   if (dict) {
     X.auto_exec = auto_exec(flags, prefix, chain);
     X.k4j_auto = X.auto_exec && auto_candidates_ok(candidates);
     X.k4j_mode = k4j_mode_plan(X.k4j_mode, flags, true, prefix, chain);
+  }
+  if (dict_j) {
+    // (the rule's width is the plan's frame count, its candidates the whole plan's)
+    const int m = dict_j_mode(flags);
+    X.auto_exec = m < 0;
+    X.k4j_auto = X.auto_exec && auto_dict_candidates_ok(candidates);
+    X.k4j_mode = m == 1 ? 1 : 0;
   }
 }
 
@@ -260,6 +281,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   uint64_t bound = 0;
   bool seqs_in_frame = false;
   const bool names_dict = hf.d.kind == ZD_FRAME_ZSTD && hf.d.dict_id != UINT64_MAX && hf.d.dict_id != 0;
+  uint32_t jsrc = 0;             // JFrame::src: the frame's entry among the plan's dictionary addresses
   if (X.dset) {
     // the frame's own dictionary: by its ID, else the fallback, else none (a
     // skippable frame: none, nothing of it reads one)
@@ -277,7 +299,8 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
       fs.rep[0] = d.rep[0]; fs.rep[1] = d.rep[1]; fs.rep[2] = d.rep[2];
       huf_prev = tab_prev[0] = tab_prev[1] = tab_prev[2] = d.comp;
     }
-    if (FILL) S.frame_dict[fi] = e >= 0 ? (uint32_t)e : X.ndset;
+    jsrc = e >= 0 ? (uint32_t)e : X.ndset;
+    if (FILL) S.frame_dict[fi] = jsrc;
   } else if (X.prefix_bytes) {
     // the frame's own prefix: raw content, so no ID fits it
     if (names_dict) fs.key = plan_min(fs.key, make_key(PH_PARSE, 0, PS_STRUCT, 0, ZD_E_DICT_MISMATCH));
@@ -419,9 +442,14 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
   // with ZD_F_BLOCK_PARALLEL sends to K4J keeps only the prefix's own limit:
   // K4J's state words number the frame's own bytes from 0 and never hold a
   // prefix position.  ZD_F_AUTO_EXECUTOR (j_auto): of the frames the flag could
-  // send there, those the rule names
-  const bool j_ok = X.prefix_bytes && !frame_failed_host && fd.nblocks && hf.ncomp && hf.d.kind == ZD_FRAME_ZSTD &&
-                    cap <= K4J_MAX_FRAME_OUT;
+  // send there, those the rule names.
+  // A dictionary plan created with ZD_F_DICT_BLOCK_PARALLEL (dict_j): the same
+  // three lines with the dictionary's content for the prefix -- it is at most
+  // ZD_DICT_MAX_CONTENT, so only the capacity can keep a frame off K4J, and the
+  // limit below stays the prefix batches' alone (a dictionary frame K4J does
+  // not take is keyed further down, as it always was)
+  const bool j_ok = (X.prefix_bytes || X.dict_j) && !frame_failed_host && fd.nblocks && hf.ncomp &&
+                    hf.d.kind == ZD_FRAME_ZSTD && cap <= K4J_MAX_FRAME_OUT;
   const bool j_auto = X.auto_exec && j_ok && plan_auto_j(hf.ncomp, X.k4j_min, X.k4j_auto, out_len0, cap);
   const bool j_pfx = j_ok && (X.k4j_mode == 1 || j_auto);
   if (X.prefix_bytes && out_len0 &&
@@ -473,6 +501,7 @@ ZD_HD void plan_frame(const PlanCtx& X, const HostFrame& hf, const HostBlock* hb
       jf.frame = fi;
       jf.jb0 = (uint32_t)J[PJ_BLK];
       jf.njb = fd.nblocks;
+      jf.src = jsrc;
       S.jframes[J[PJ_FRAMES]] = jf;
     }
     if (jm) jm->note(nseq);

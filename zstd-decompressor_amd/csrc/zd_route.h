@@ -111,6 +111,20 @@ inline bool auto_exec(uint32_t flags, bool prefix, bool chain) {
   return prefix && (flags & ZD_F_AUTO_EXECUTOR) &&
          !(flags & (chain ? ZD_F_CHAIN_BLOCK_PARALLEL : ZD_F_BLOCK_PARALLEL | ZD_F_FRAME_SERIAL));
 }
+// ZD_F_DICT_BLOCK_PARALLEL holds: a dictionary or dictionary-set plan or batch
+// (`dictionary`: not a prefix or chain batch) created with it.  The functions
+// above keep their answers for such a plan (its k4j_mode_behind stays 0): what
+// it sends to K4J is dict_j_mode's -- 0 no frame (ZD_F_FRAME_SERIAL), 1 every
+// frame with a compressed block (ZD_F_BLOCK_PARALLEL), < 0 each frame by
+// plan_auto_j (zd_plan.h).  ZD_K4J is not read for it.
+inline bool dict_j(uint32_t flags, bool dictionary) { return dictionary && (flags & ZD_F_DICT_BLOCK_PARALLEL) != 0; }
+inline int dict_j_mode(uint32_t flags) {
+  return (flags & ZD_F_FRAME_SERIAL) ? 0 : (flags & ZD_F_BLOCK_PARALLEL) ? 1 : -1;
+}
+// (the rule's candidate cap behind a dictionary: auto_candidates_ok with the dictionary plans' own constant)
+inline bool auto_dict_candidates_ok(uint64_t candidates) {
+  return candidates > 0 && candidates <= ZD_AUTO_DICT_MAX_CANDIDATES;
+}
 // A chain batch laid out for K4J level by level (J frames numbered level-major,
 // launches and pend words per level): forced or automatic
 inline bool chain_j_layout(uint32_t flags, bool chain) { return chain_j(flags, chain) || (chain && auto_exec(flags, true, true)); }

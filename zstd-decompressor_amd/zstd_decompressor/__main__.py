@@ -21,6 +21,9 @@ to its Content_Checksum ends the run with `Error: frame N: ChecksumWrong`
 content), as zstd's own -D does; -D given several times makes a dictionary
 set: every frame decodes with the dictionary its Dictionary_ID names, a frame
 without an ID with the one raw-content file if there is one, else the first.
+When some frame's Frame_Content_Size is at least 2 MiB (--patch-from's
+threshold below) the plan is created with F_DICT_BLOCK_PARALLEL, so that its
+frames of several blocks decode block-parallel; the output is the same.
 --patch-from OLD decodes FILE, one frame made by `zstd --patch-from OLD`,
 against the bytes of OLD as its prefix (raw content, whatever they start
 with): a prefix batch of one chunk with OLD uploaded.  The output is written
@@ -260,8 +263,15 @@ def main(argv=None) -> int:
     except _lib.ZdError as e:
         print(f"Error: dictionary: {e.name}", file=sys.stderr)
         return 1
+    flags = _plan_flags(a)
+    if dictionary is not None:
+        # a frame of --patch-from's threshold behind a dictionary: the plan may send its frames to the
+        # block-parallel executor, each by the library's rule (the same bytes either way)
+        sized = [f["content_size"] for f in frames_index(data)[0] if f["kind"] != 1]
+        if any(cs != (1 << 64) - 1 and cs >= PATCH_BLOCK_PARALLEL_BYTES for cs in sized):
+            flags |= _lib.F_DICT_BLOCK_PARALLEL
     plan = Plan(data, a.print_skippable,
-                _plan_flags(a),
+                flags,
                 dictionary=dictionary)
     dev = torch.device("cuda", torch.cuda.current_device())
     d_src = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)

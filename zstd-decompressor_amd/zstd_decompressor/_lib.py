@@ -335,7 +335,9 @@ SEEK_RFC = 4           # zd_seekable_read_create_ex read_flags: the inner batch 
 SEEK_VERIFY_TABLE = 1  # zd_seekable_read_create_ex read_flags: the seek table's Checksums verified inside the launch
 SIZES_DICT = 1         # zd_chunk_sizes_device: the chunks will be decoded with a dictionary or set
 F_RFC = 16384           # frames decode as RFC 8878 / libzstd have them (default: the reference's decoder, D1-D3, D8)
-SIZES_RFC = 16384        # zd_chunk_sizes_device: the chunks will be decoded with F_RFC (the same bit)
+F_DICT_BLOCK_PARALLEL = 32768  # a dictionary / set plan or batch: frames may run on K4J (with F_BLOCK_PARALLEL every
+                               # frame with a compressed block, with F_FRAME_SERIAL none, else by the ZD_AUTO_* rule)
+SIZES_RFC = 16384       # zd_chunk_sizes_device: the chunks will be decoded with F_RFC (the same bit)
 SIZES_MULTI_FRAME = 8    # zd_chunk_sizes_device: the chunks may hold several frames (a MultiFrameBatch will decode them)
 SIZES_LONG_WINDOW = 2048  # zd_chunk_sizes_device: the chunks will be decoded with F_LONG_WINDOW (the same bit)
 EXEC_FUSED, EXEC_K4F, EXEC_K4J = 1, 2, 4  # zd_plan_info.executors bits (include/zd.h ZD_EXEC_*)

@@ -126,15 +126,18 @@ def _decompress(data: bytes, flags: int, dictionary=None):
 
 
 def decompress(data: bytes, print_skippable: bool = False, dictionary=None, verify: bool = False,
-               rfc: bool = False) -> bytes:
+               rfc: bool = False, flags: int = 0) -> bytes:
     """Decode every frame of `data` on the GPU (host in, host out);
     dictionary: a Dictionary every frame decodes with, or a DictionarySet;
     verify: a frame whose bytes do not hash to its Content_Checksum raises
     ZdError(CHECKSUM_WRONG), as libzstd fails such a frame; rfc: frames decode
     as RFC 8878 and libzstd have them (F_RFC), where the default is the
-    reference's decoder, which fails or corrupts some frames libzstd writes."""
-    flags = ((_lib.F_SKIPPABLE if print_skippable else 0) | (_lib.F_VERIFY_CHECKSUM if verify else 0) |
-             (_lib.F_RFC if rfc else 0))
+    reference's decoder, which fails or corrupts some frames libzstd writes;
+    flags: extra plan flags, such as _lib.F_DICT_BLOCK_PARALLEL with
+    dictionary= (large frames behind a dictionary on the block-parallel
+    executor; the same bytes)."""
+    flags |= ((_lib.F_SKIPPABLE if print_skippable else 0) | (_lib.F_VERIFY_CHECKSUM if verify else 0) |
+              (_lib.F_RFC if rfc else 0))
     st, out = _decompress(data, flags, dictionary)
     _lib.check(st, "zd_decompress")
     return out
@@ -370,6 +373,9 @@ class Batch:
     flags: with prefixes= or parents=, _lib.F_AUTO_EXECUTOR routes each chunk's
     frame on its own (large frames to the block-parallel executor, the rest to
     the streaming one); `info.k4j_chunks` counts the former in any batch.
+    With dictionary=, _lib.F_DICT_BLOCK_PARALLEL lets frames run on the
+    block-parallel executor: all with a compressed block under
+    F_BLOCK_PARALLEL, none under F_FRAME_SERIAL, else by the same rule.
 
     src_ptrs / dst_ptrs are device addresses (integers, e.g. tensor.data_ptr()),
     src_sizes / dst_caps byte counts.  A chunk holds one zstd frame (skippable
